@@ -5,12 +5,18 @@ One "step" = one scene through GenComm (q_sample + T x0-parameterised ancestral 
 the diffusion UNet) -> Enhancer -> warp + AttFusion, on synthetic tensors already resident in HBM.
 Workload = BASELINE.json's metric configuration: 4 agents, C=64, 200x704 BEV, T=20.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Scenes are independent, so N GPUs = N replicas each running its own scenes (no data-path
 collective; weak scaling). Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` and `ms_per_step` come from those K steps alone.
+`--full` adds everything measured or checked beside that figure, each in runs of its own after the K steps: the sustained repeat,
+the single-scene latency, the per-kernel-family rooflines, the exact-fp32 pass and the CPU baseline (training leg: the roofline
+step and the CPU baseline). `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32; a fixed,
+seeded sample of the values of a large output), so that two builds can be compared output for output on identical inputs.
 
 `python bench.py --gpus N` without torch.distributed.run starts its own N ranks (gencomm_amd/launch.py) before the parent
 makes any GPU call; under torch.distributed.run the environment it set is used as is. `--share-device` puts every rank on
@@ -60,6 +66,22 @@ ENH_FRONT_FAMILY = 9
 N_FAMILIES = 20
 CONV2D_FAMILY = 19      # the general convolution around the path (conv2d_h3l / conv2d_h3 / conv2d_igemm kernels): its timer slot carries algorithmic FLOPs
 RESULT_OUT = sys.stdout   # main() replaces it by a private copy of the original stdout
+DUMP_MAX_VALUES = 12 << 20   # --dump-outputs: float32 values over all files of a run (48 MiB)
+
+
+def dump_outputs(out_dir, arrays):
+    """`arrays`: name -> device tensor. Writes out_dir/<name>.npy in float32. The value budget is shared equally among the
+    arrays; an array with more values than its share is written as the values at a fixed, seeded sample of sorted flat
+    positions, which depends only on the array's size, so two runs with the same arguments sample the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_VALUES // max(1, len(arrays))
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            pos = np.random.default_rng(0).choice(flat.numel(), size=share, replace=False)
+            pos.sort()
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.float().cpu().numpy())
 
 
 def algorithmic_work(N, C, HW, T):
@@ -273,6 +295,7 @@ def train_main(args, rank, world, device, backend):
     data = {"agent_modality_list": ["m1"] * n, "record_len": torch.tensor([N] * B), "pairwise_t_matrix": torch.from_numpy(ptm).to(device),
             "inputs_m1": {k: torch.from_numpy(pil[k]).to(device) for k in ("voxel_features", "voxel_coords", "voxel_num_points")}}
     labels = None
+    last = {}          # --dump-outputs: the step's loss and forward outputs (in a captured graph: its static tensors)
 
     def step():
         nonlocal labels
@@ -283,6 +306,8 @@ def train_main(args, rank, world, device, backend):
             li = synth.make_loss_inputs(50 + rank, B, Hh, Wh, A, 1)
             labels = {k: torch.from_numpy(li[k]).to(device) for k in ("pos_equal_one", "neg_equal_one", "targets")}
         loss = crit(out, labels)
+        if args.dump_outputs:
+            last.update(out, loss=loss)
         loss.backward()
         if sync is not None:
             sync.sync()
@@ -416,22 +441,25 @@ def train_main(args, rank, world, device, backend):
     barrier()
     elapsed_here = time.perf_counter() - t0
     assert torch.isfinite(loss.detach()).all(), "non-finite training loss"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v for k, v in last.items() if torch.is_tensor(v) and v.is_floating_point()})
     value, elapsed, total_scenes = gdist.aggregate_throughput(args.steps * B, elapsed_here, dist, red_dev)
     grad_bytes = sum(p.numel() * p.element_size() for p in params) if sync is None else sync.bucket_bytes
     # roofline of the step's dominant kernel family -- the general convolution (BEV backbone, shrink conv, heads, the Enhancer's Linear
     # layers; forward and input gradients): HIP-event time and algorithmic FLOPs of every launch of ONE extra eager step (the library's
     # kernel timer, family CONV2D_FAMILY), priced against the f16 pipe's peak over the six matrix instructions of a product block
     roofline = None
-    if rank == 0:
+    if args.full and rank == 0:
         from gencomm_amd import _lib
         lib = _lib.lib()
         ms = (ctypes.c_double * N_FAMILIES)()
         cnt = (ctypes.c_int * N_FAMILIES)()
         wk = (ctypes.c_double * N_FAMILIES)()
         _lib.check(lib.gencomm_timer_start_mask(1 << CONV2D_FAMILY, 4096), "gencomm_timer_start_mask")
-    eager_step()        # EVERY rank runs the extra step (it contains the gradient collective); only rank 0's launches are timed
-    barrier()
-    if rank == 0:
+    if args.full:
+        eager_step()        # EVERY rank runs the extra step (it contains the gradient collective); only rank 0's launches are timed
+        barrier()
+    if args.full and rank == 0:
         _lib.check(lib.gencomm_timer_stop_families(ms, cnt, wk, N_FAMILIES), "gencomm_timer_stop_families")
         if cnt[CONV2D_FAMILY] > 0:
             f_ms, f_fl, f_n = ms[CONV2D_FAMILY], wk[CONV2D_FAMILY], cnt[CONV2D_FAMILY]
@@ -448,7 +476,7 @@ def train_main(args, rank, world, device, backend):
                                 "isolated-kernel times); peak = the f16 pipe's 2 500 TFLOP/s over the six matrix instructions of a product block; "
                                 "share_of_step = the family's summed device time over the step's wall time"}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_train_baseline(B, N, 128, 64, 128, T, model)
     if rank == 0:
         from gencomm_amd import _lib as _lib_modes
@@ -478,6 +506,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="metric", choices=sorted(WORKLOADS) + ["train", "launch_selftest"])
+    ap.add_argument("--full", action="store_true",
+                    help="besides the K timed steps: sustained repeat, single-scene latency, per-kernel-family rooflines, exact-fp32 pass, "
+                         "CPU baseline (--workload train: roofline step, CPU baseline); the --no-* options below thin it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0, float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-enhancer", action="store_true")
     ap.add_argument("--no-exact", action="store_true", help="skip the exact-fp32 pass (profiling runs)")
@@ -504,6 +537,8 @@ def main():
     ap.add_argument("--train-agents", type=int, default=2, help="--workload train: agents per scene")
     ap.add_argument("--launch-timeout", type=float, default=None, help="seconds before the self-launcher stops its ranks")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload == "launch_selftest":
+        ap.error("--dump-outputs: --workload launch_selftest computes nothing to write")
 
     from gencomm_amd import dist as gdist
     from gencomm_amd import launch
@@ -698,17 +733,20 @@ def main():
             torch.cuda.set_sync_debug_mode("default")
             torch.cuda.synchronize(device)
         elapsed = timed_region(args.steps, 2000)
+        if args.dump_outputs and rank == 0:     # step i ran on pipes[i % S]; nothing below runs before this
+            last = pipes[(args.steps - 1) % S]
+            dump_outputs(args.dump_outputs, {"fused": last.fused, "pred_feature": last.pred})
         # the K-step region above is the reported number; 20 steps = 0.4 s is too short for a 5 s-period utilisation sampler to
         # see, so the same loop is repeated to >= --sustain seconds (default 12: at least two sampler periods) in ONE bracket and
         # reported beside it -- `value` stays on the K-step region
         sustained = None
-        if elapsed < args.sustain and not args.no_timer:   # profiling runs (--no-timer) execute the K-step region only
+        if args.full and elapsed < args.sustain and not args.no_timer:   # profiling runs (--no-timer) execute the K-step region only
             reps = int(np.ceil(args.sustain / max(elapsed, 1e-3)))
             ts = timed_region(args.steps * reps, 2500)
             sustained = {"steps": args.steps * reps, "seconds": ts, "value_this_rank": args.steps * reps * B / ts, "unit": "scenes/sec"}
         # latency of ONE scene alone (one stream, batch 1): throughput above needs S x B scenes in flight
         latency = None
-        if rank == 0 and not args.no_timer:
+        if args.full and rank == 0 and not args.no_timer:
             f1, c1, p1 = make_scene(N, C, H, W, 77, device, 1)
             pipe1 = ScenePipeline(gen, None if args.no_enhancer else enh, [N], C, H, W, device)
             pipe1.set_affine(normalize_pairwise_tfm(p1, H * PX_M, W * PX_M, 1))
@@ -721,7 +759,7 @@ def main():
             torch.cuda.synchronize(device)
             latency = 1e3 * (time.perf_counter() - t0) / 10
             del pipe1, f1, c1
-    timed = rank == 0 and not args.graph and not args.no_timer  # event pairs cannot be recorded into a replayed graph
+    timed = args.full and rank == 0 and not args.graph and not args.no_timer  # event pairs cannot be recorded into a replayed graph
     arith_mode = lib.gencomm_get_mode(_lib.MODE_ARITH)
     split_default = arith_mode in (0, 3)   # 3 = 0 on this path (the opt-in two-term kernels are the general convolutions AROUND it)
     roofs = rooflines(family_pass(), "Arithmetic: see config.arithmetic.") if timed else {}
@@ -729,7 +767,7 @@ def main():
     # the same workload with the exact-fp32 MFMA kernels everywhere, the arithmetic that is identical to the reference's:
     # the full step count, timed the same way (rank 0), with its own family pass
     exact = None
-    if rank == 0 and split_default and not args.no_exact:
+    if args.full and rank == 0 and split_default and not args.no_exact:
         with _lib.mode(_lib.MODE_ARITH, 1), torch.no_grad():
             for i in range(S):
                 run_scene(i, 4000 + i)
@@ -789,7 +827,7 @@ def main():
         out["roofline_enh_front"] = roofs.get("roofline_enh_front")
         out["kernel_time_shares"] = roofs.get("kernel_time_shares")
         out["exact_fp32_mode"] = exact
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, N, C, H, W, T, gen, enh, ptm)
         else:
             out["cpu_baseline"] = None

@@ -2,12 +2,11 @@
 build's model shell from every yaml the reference ships under opencood/hypes_yaml/**/GenComm_yamls/** (101 files) and records
 the checkpoint-key count + a hash of the sorted (key, shape) pairs, or the reason a shell cannot be built. CPU only.
 
-Where the reference checkout is mounted the sweep is re-run and must reproduce the committed report; elsewhere (the GPU box)
-the report itself is checked: every GenComm yaml is either built or refused with a reason that names the yaml key."""
+The sweep is re-run on the yamls' `model` blocks stored beside the report (tests/golden/yaml_sweep_models.json.gz, written by the same
+script) and must reproduce the committed report; the report itself is checked too: every GenComm yaml is either built or refused
+with a reason that names the yaml key."""
 import json
 import os
-
-import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPORT = os.path.join(HERE, "golden", "yaml_sweep.json")
@@ -42,9 +41,10 @@ def test_report_covers_every_shipped_gencomm_yaml_and_names_every_refusal():
     assert rep["opv2v/GenComm_yamls/gencomm/stage1/m1_att.yaml"]["hash"] == rep["dairv2x/GenComm_yamls/gencomm/stage1/m1_att.yaml"]["hash"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/opencood/hypes_yaml"), reason="the reference checkout is not mounted here")
 def test_sweep_reproduces_the_committed_report():
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(HERE), "oracle"))
     import sweep_yamls
-    assert sweep_yamls.sweep() == _report()
+    models = sweep_yamls.load_models()
+    assert sorted(models) == sorted(_report())
+    assert sweep_yamls.sweep(models) == _report()

@@ -7,7 +7,7 @@ set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out; mkdir -p $O
 step() { echo "== $1"; }
-step "bench default"; timeout -k 10 400 python bench.py > $O/r4_bench_default.json 2> $O/r4_bench_default.err || { tail -n 20 $O/r4_bench_default.err; exit 1; }
+step "bench default"; timeout -k 10 400 python bench.py --full > $O/r4_bench_default.json 2> $O/r4_bench_default.err || { tail -n 20 $O/r4_bench_default.err; exit 1; }
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r4_bench_default.json"))
@@ -16,16 +16,16 @@ print("default: %.1f scenes/s, ms/step %.2f, latency one scene %.2f ms, sustaine
     d["roofline"]["traffic"], d["roofline_latent_step"]["avg_launch_ms"], d["exact_fp32_mode"]["value"], d["cpu_baseline"]["value"], d["cpu_baseline"]["cores"]))
 PY
 for wl in cfg2 shipped v2xreal; do
-  step "bench $wl"; timeout -k 10 300 python bench.py --workload $wl --no-cpu-baseline > $O/r4_bench_$wl.json 2> $O/r4_bench_$wl.err || { tail -n 20 $O/r4_bench_$wl.err; exit 1; }
+  step "bench $wl"; timeout -k 10 300 python bench.py --full --workload $wl --no-cpu-baseline > $O/r4_bench_$wl.json 2> $O/r4_bench_$wl.err || { tail -n 20 $O/r4_bench_$wl.err; exit 1; }
   python -c "
 import json;d=json.load(open('gpurun_out/r4_bench_$wl.json'));print('$wl: %.1f scenes/s, latency one scene %.3f ms'%(d['value'],d['latency_ms_one_scene']))"
 done
 step "bench --gpus 2 --share-device (self-launched)"; timeout -k 10 300 python bench.py --gpus 2 --share-device --steps 20 --warmup 3 --no-exact --no-timer > $O/r4_bench_share2.json 2> $O/r4_bench_share2.err || { tail -n 20 $O/r4_bench_share2.err; exit 1; }
 python -c "
 import json;d=json.load(open('gpurun_out/r4_bench_share2.json'));print('share2: %.1f scenes/s over %d ranks, %d scenes, group %s'%(d['value'],d['n_gpus'],d['total_scenes'],d['config']['process_group']))"
-step "train leg N=1 (RCCL, world 1)"; timeout -k 10 400 python bench.py --workload train --steps 20 --warmup 3 > $O/r4_train_leg_n1.json 2> $O/r4_train_leg_n1.err || { tail -n 30 $O/r4_train_leg_n1.err; exit 1; }
-step "train leg N=1 under torch DistributedDataParallel"; timeout -k 10 400 python bench.py --workload train --grad-sync ddp --steps 20 --warmup 3 > $O/r4_train_leg_n1_ddp.json 2> $O/r4_train_leg_n1_ddp.err || { tail -n 30 $O/r4_train_leg_n1_ddp.err; exit 1; }
-step "train leg N=2 share-device (gloo)"; timeout -k 10 400 python bench.py --workload train --gpus 2 --share-device --steps 10 --warmup 3 > $O/r4_train_leg_share2.json 2> $O/r4_train_leg_share2.err || { tail -n 30 $O/r4_train_leg_share2.err; exit 1; }
+step "train leg N=1 (RCCL, world 1)"; timeout -k 10 400 python bench.py --full --workload train --steps 20 --warmup 3 > $O/r4_train_leg_n1.json 2> $O/r4_train_leg_n1.err || { tail -n 30 $O/r4_train_leg_n1.err; exit 1; }
+step "train leg N=1 under torch DistributedDataParallel"; timeout -k 10 400 python bench.py --full --workload train --grad-sync ddp --steps 20 --warmup 3 > $O/r4_train_leg_n1_ddp.json 2> $O/r4_train_leg_n1_ddp.err || { tail -n 30 $O/r4_train_leg_n1_ddp.err; exit 1; }
+step "train leg N=2 share-device (gloo)"; timeout -k 10 400 python bench.py --full --workload train --gpus 2 --share-device --steps 10 --warmup 3 > $O/r4_train_leg_share2.json 2> $O/r4_train_leg_share2.err || { tail -n 30 $O/r4_train_leg_share2.err; exit 1; }
 python - <<'PY'
 import json
 for f in ("n1","n1_ddp","share2"):
@@ -45,7 +45,7 @@ timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r4_
 find $O/r4_prof_train -name "*kernel_stats.csv" -exec cp {} $O/r4_train_step_kernel_stats.csv \;
 rm -rf $O/r4_prof_train
 step "rocprof train leg"; rm -rf $O/r4_prof_leg
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r4_prof_leg -o k -- python3 bench.py --workload train --steps 5 --warmup 2 > $O/r4_prof_leg.log 2>&1 || { tail -n 20 $O/r4_prof_leg.log; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r4_prof_leg -o k -- python3 bench.py --full --workload train --steps 5 --warmup 2 > $O/r4_prof_leg.log 2>&1 || { tail -n 20 $O/r4_prof_leg.log; exit 1; }
 find $O/r4_prof_leg -name "*kernel_stats.csv" -exec cp {} $O/r4_train_leg_kernel_stats.csv \;
 rm -rf $O/r4_prof_leg
 step "pmc traffic"; bash tools/pmc_pass.sh metric > $O/r4_pmc_pass.log 2>&1 || { tail -n 20 $O/r4_pmc_pass.log; exit 1; }
@@ -55,7 +55,7 @@ rm -rf $O/r4_pmc_FETCH_SIZE $O/r4_pmc_WRITE_SIZE $O/r4_pmc_SQ $O/r4_pmc_INSTS
 step "parity margins"; timeout -k 10 600 python -m pytest tests/test_gpu_philox_replay.py tests/test_gpu_configs.py -m gpu -q -s -k "metric" > $O/r4_parity.log 2>&1 || { tail -n 20 $O/r4_parity.log; exit 1; }
 grep -E "vs float64|vs float32 oracle" $O/r4_parity.log > $O/r4_parity_margins.txt; cat $O/r4_parity_margins.txt | cut -c1-260
 step "bench default again (traffic and issue now stamped)"; cp $O/r4_pmc_traffic.json profiles/r4_pmc_traffic.json; cp $O/r4_pmc_sq.json profiles/r4_pmc_sq.json
-timeout -k 10 400 python bench.py > $O/r4_bench_default.json 2> $O/r4_bench_default.err || { tail -n 20 $O/r4_bench_default.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/r4_bench_default.json 2> $O/r4_bench_default.err || { tail -n 20 $O/r4_bench_default.err; exit 1; }
 python -c "
 import json;d=json.load(open('gpurun_out/r4_bench_default.json'));print('default (2nd): %.1f scenes/s, frac %.3f, traffic %s (%s)'%(d['value'],d['roofline']['frac'],d['roofline']['traffic'],d['roofline']['traffic_source']))"
 echo done

@@ -5,10 +5,10 @@ set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out; mkdir -p $O
 step() { echo "== $1"; }
-step "train leg N=1 (RCCL, world 1)"; timeout -k 10 400 python bench.py --workload train --steps 20 --warmup 3 > $O/r5_train_leg_n1.json 2> $O/r5_train_leg_n1.err || { tail -n 30 $O/r5_train_leg_n1.err; exit 1; }
-step "train leg N=1 under torch DistributedDataParallel"; timeout -k 10 400 python bench.py --workload train --grad-sync ddp --steps 20 --warmup 3 --no-cpu-baseline > $O/r5_train_leg_n1_ddp.json 2> $O/r5_train_leg_n1_ddp.err || { tail -n 30 $O/r5_train_leg_n1_ddp.err; exit 1; }
-step "train leg N=4 share-device (gloo)"; timeout -k 10 400 python bench.py --workload train --gpus 4 --share-device --steps 10 --warmup 3 --no-cpu-baseline > $O/r5_train_leg_share4.json 2> $O/r5_train_leg_share4.err || { tail -n 30 $O/r5_train_leg_share4.err; exit 1; }
-step "train leg N=1, exact fp32 (GENCOMM_MODE_ARITH = 1)"; timeout -k 10 400 python bench.py --workload train --steps 20 --warmup 3 --no-cpu-baseline --mode arith=1 > $O/r5_train_leg_n1_exact.json 2> $O/r5_train_leg_n1_exact.err || { tail -n 30 $O/r5_train_leg_n1_exact.err; exit 1; }
+step "train leg N=1 (RCCL, world 1)"; timeout -k 10 400 python bench.py --full --workload train --steps 20 --warmup 3 > $O/r5_train_leg_n1.json 2> $O/r5_train_leg_n1.err || { tail -n 30 $O/r5_train_leg_n1.err; exit 1; }
+step "train leg N=1 under torch DistributedDataParallel"; timeout -k 10 400 python bench.py --full --workload train --grad-sync ddp --steps 20 --warmup 3 --no-cpu-baseline > $O/r5_train_leg_n1_ddp.json 2> $O/r5_train_leg_n1_ddp.err || { tail -n 30 $O/r5_train_leg_n1_ddp.err; exit 1; }
+step "train leg N=4 share-device (gloo)"; timeout -k 10 400 python bench.py --full --workload train --gpus 4 --share-device --steps 10 --warmup 3 --no-cpu-baseline > $O/r5_train_leg_share4.json 2> $O/r5_train_leg_share4.err || { tail -n 30 $O/r5_train_leg_share4.err; exit 1; }
+step "train leg N=1, exact fp32 (GENCOMM_MODE_ARITH = 1)"; timeout -k 10 400 python bench.py --full --workload train --steps 20 --warmup 3 --no-cpu-baseline --mode arith=1 > $O/r5_train_leg_n1_exact.json 2> $O/r5_train_leg_n1_exact.err || { tail -n 30 $O/r5_train_leg_n1_exact.err; exit 1; }
 python - <<'PY'
 import json
 for f in ("n1","n1_ddp","share4","n1_exact"):
@@ -26,7 +26,7 @@ timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r5_
 find $O/r5_prof_train -name "*kernel_stats.csv" -exec cp {} $O/r5_train_step_kernel_stats.csv \;
 rm -rf $O/r5_prof_train
 step "rocprof train leg"; rm -rf $O/r5_prof_leg
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r5_prof_leg -o k -- python3 bench.py --workload train --steps 5 --warmup 2 --no-cpu-baseline --no-timer > $O/r5_prof_leg.log 2>&1 || { tail -n 20 $O/r5_prof_leg.log; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r5_prof_leg -o k -- python3 bench.py --full --workload train --steps 5 --warmup 2 --no-cpu-baseline --no-timer > $O/r5_prof_leg.log 2>&1 || { tail -n 20 $O/r5_prof_leg.log; exit 1; }
 find $O/r5_prof_leg -name "*kernel_stats.csv" -exec cp {} $O/r5_train_leg_kernel_stats.csv \;
 python tools/trace_by_grid.py $(find $O/r5_prof_leg -name "*kernel_trace.csv" | head -1) > $O/r5_train_leg_kernel_stats_by_grid.csv
 rm -rf $O/r5_prof_leg

@@ -21,7 +21,7 @@ rm -rf $O/r5_pmc_FETCH_SIZE $O/r5_pmc_WRITE_SIZE $O/r5_pmc_SQ $O/r5_pmc_INSTS
 step "parity margins"; timeout -k 10 600 python -m pytest tests/test_gpu_philox_replay.py tests/test_gpu_configs.py -m gpu -q -s -k "metric" > $O/r5_parity.log 2>&1 || { tail -n 20 $O/r5_parity.log; exit 1; }
 grep -E "vs float64|vs float32 oracle" $O/r5_parity.log > $O/r5_parity_margins.txt; cat $O/r5_parity_margins.txt | cut -c1-260
 step "bench default again (traffic and issue now stamped)"; cp $O/r5_pmc_traffic.json profiles/r5_pmc_traffic.json; cp $O/r5_pmc_sq.json profiles/r5_pmc_sq.json
-timeout -k 10 400 python bench.py > $O/r5_bench_default.json 2> $O/r5_bench_default.err || { tail -n 20 $O/r5_bench_default.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/r5_bench_default.json 2> $O/r5_bench_default.err || { tail -n 20 $O/r5_bench_default.err; exit 1; }
 python -c "
 import json;d=json.load(open('gpurun_out/r5_bench_default.json'));print('default (stamped): %.1f scenes/s, sustained %.1f, frac %.3f, traffic %s (%s), issue %s'%(d['value'],d['sustained']['value_this_rank'],d['roofline']['frac'],d['roofline']['traffic'],d['roofline'].get('traffic_source'),str(d['roofline'].get('issue'))[:120]))"
 echo done
