@@ -15,7 +15,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("GENCOMM_HIP_LIB", os.path.join(PKG_DIR, "libgencomm_hip.so"))  # override: diagnostic builds only
-ABI_VERSION = 11
+ABI_VERSION = 12
 MODE_ARITH, MODE_SAMPLER, MODE_TILE_WANT, MODE_ENH_FUSE, MODE_CONV8H_MASK, MODE_XCD_REMAP, MODE_DATAFLOW, MODE_RESFUSE_EMU, MODE_TILE8, MODE_BWD_STREAMS, MODE_PERSIST = range(11)
 
 _lock = threading.Lock()
@@ -150,6 +150,10 @@ _SIGNATURES = {
     "gencomm_warp_attfuse_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "gencomm_warp_maxfuse_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "gencomm_warp_attfuse_tok_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "gencomm_lss_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
+    "gencomm_lss_splat_fwd": (_i, [_p] * 8 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_i)] + [_i] * 6 + [_p, _p, _p, _ll, _p]),
+    "gencomm_lss_depth_target_fwd": (_i, [_p, _i, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _p, _p, _p]),
+    "gencomm_maxpool3x3s2_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -1,5 +1,5 @@
 // Second translation unit of libgencomm_hip.so: iou3d_nms (reference extension semantics), the point-cloud voxeliser,
-// the V2X-ViT attention kernels and the sparse 3-D convolutions of the SECOND encoder.
+// the V2X-ViT attention kernels, the sparse 3-D convolutions of the SECOND encoder and the Lift-Splat-Shoot camera encoder.
 // Kept apart from gencomm_abi.hip so that the rocPRIM templates do not lengthen the hot path's compile.
 #include "../../include/gencomm_hip.h"
 
@@ -8,6 +8,7 @@
 #include "common.h"
 #include "iou3d_kernels.h"
 #include "loss_kernels.h"
+#include "lss_kernels.h"
 #include "sparse_kernels.h"
 #include "v2xvit_kernels.h"
 #include "voxel_kernels.h"
@@ -417,6 +418,99 @@ int gencomm_head_loss(const float* cls, const float* reg, const float* dir, cons
   a.dir_weight = dir_weight; a.inv_bs = 1.0f / (float)batch_size; a.dir_offset = dir_offset;
   for (int i = 0; i < kLossMaxAnchors; ++i) a.anchor_yaw[i] = (dir != nullptr && i < A) ? anchor_yaw[i] : 0.0;
   return head_loss_enqueue(a, (hipStream_t)stream);
+}
+
+// ---- Lift-Splat-Shoot camera encoder ---------------------------------------------------------------------------------
+static int lss_geom(LssGeom& g, int B, int N, int D, int fH, int fW, int C, const float* lo3, const float* dx3, const int* nx3) {
+  GC_CHECK_ARG(lo3 && dx3 && nx3, "null pointer");
+  GC_CHECK_ARG(B >= 1 && N >= 1 && D >= 1 && fH >= 1 && fW >= 1 && C >= 1, "bad B / N / D / fH / fW / C");
+  GC_CHECK_ARG(nx3[0] >= 1 && nx3[1] >= 1 && nx3[2] >= 1 && B <= 65535 && nx3[1] <= 65535 && (long long)B * nx3[2] <= 65535, "bad grid");
+  GC_CHECK_ARG((long long)B * nx3[0] * nx3[1] * nx3[2] < (1LL << 31) - 1, "grid has too many cells for 32-bit ranks");
+  GC_CHECK_ARG((long long)B * N * D * fH * fW < (1LL << 31), "too many frustum points");
+  GC_CHECK_ARG((long long)B * N * fH * fW * C < (1LL << 40), "feature map too large");
+  for (int j = 0; j < 3; ++j) {
+    GC_CHECK_ARG(dx3[j] > 0.f, "cell size must be positive");
+    g.lo[j] = lo3[j];
+    g.dx[j] = dx3[j];
+  }
+  g.nx = nx3[0]; g.ny = nx3[1]; g.nz = nx3[2];
+  g.B = B; g.N = N; g.D = D; g.fH = fH; g.fW = fW; g.C = C;
+  return GC_OK;
+}
+static int lss_sort_bits(const LssGeom& g) {
+  const unsigned long long ncells = (unsigned long long)g.B * g.nx * g.ny * g.nz;   // the sentinel key of out-of-grid points
+  int bits = 1;
+  while ((1ULL << bits) <= ncells) ++bits;
+  return bits;
+}
+
+long long gencomm_lss_workspace_bytes(int B, int N, int D, int fH, int fW, int C, const int* nx3) {
+  const float lo[3] = {0.f, 0.f, 0.f}, dx[3] = {1.f, 1.f, 1.f};
+  LssGeom g{};
+  if (lss_geom(g, B, N, D, fH, fW, C, lo, dx, nx3) != GC_OK) return -1;
+  const long long pixels = (long long)B * N * fH * fW;
+  return (long long)lss_ws(pixels * D, pixels, C, lss_sort_bits(g)).total;
+}
+
+int gencomm_lss_splat_fwd(const float* depth_logit, const float* feat, const float* frustum, const float* rots, const float* trans,
+                          const float* intrins, const float* post_rots, const float* post_trans, const float* lo3, const float* dx3,
+                          const int* nx3, int B, int N, int D, int fH, int fW, int C, float* out, int* cell, void* workspace,
+                          long long workspace_bytes, void* stream) {
+  LssGeom g{};
+  if (int rc = lss_geom(g, B, N, D, fH, fW, C, lo3, dx3, nx3)) return rc;
+  GC_CHECK_ARG(depth_logit && feat && frustum && rots && trans && intrins && post_rots && post_trans && out && workspace, "null pointer");
+  const long long pixels = (long long)B * N * fH * fW, npts = pixels * D;
+  const int bits = lss_sort_bits(g);
+  const LssWs w = lss_ws(npts, pixels, C, bits);
+  if ((long long)w.total > workspace_bytes) return fail(GC_ERR_WORKSPACE, "workspace too small (gencomm_lss_workspace_bytes)");
+  hipStream_t st = (hipStream_t)stream;
+  char* wsp = (char*)workspace;
+  float* featT = reinterpret_cast<float*>(wsp + w.featT);
+  float* prob = reinterpret_cast<float*>(wsp + w.prob);
+  unsigned* key = reinterpret_cast<unsigned*>(wsp + w.key);
+  unsigned* skey = reinterpret_cast<unsigned*>(wsp + w.skey);
+  int* val = reinterpret_cast<int*>(wsp + w.val);
+  int* sval = reinterpret_cast<int*>(wsp + w.sval);
+  GC_KLOG("lss_lift_kernel");
+  lss_lift_kernel<<<(unsigned)((pixels + 63) / 64), 64, 0, st>>>(depth_logit, feat, frustum, rots, trans, intrins, post_rots, post_trans, g,
+                                                                 prob, featT, key, val, cell);
+  GC_HIP(hipGetLastError());
+  size_t tb = w.temp_bytes;
+  GC_HIP(rocprim::radix_sort_pairs(wsp + w.temp, tb, key, skey, val, sval, (size_t)npts, 0, bits, st));   // stable: ties keep point order
+  GC_KLOG("lss_splat_kernel");
+  lss_splat_kernel<<<dim3((g.nx + kLssTx - 1) / kLssTx, g.ny, g.B * g.nz), 256, 0, st>>>(skey, sval, (int)npts, prob, featT, g, out);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_lss_depth_target_fwd(const float* imgs, int BN, int Cimg, int H, int W, int downsample, int mode, float d_min, float d_max,
+                                 int num_bins, long long* indices, unsigned char* mask, void* stream) {
+  GC_CHECK_ARG(imgs && indices, "null pointer");
+  GC_CHECK_ARG(BN >= 1 && Cimg >= 4 && H >= 1 && W >= 1 && downsample >= 1 && num_bins >= 1 && (mode == 0 || mode == 1), "bad dims / mode");
+  LssDepthArgs a{};
+  a.imgs = imgs; a.idx = indices; a.mask = mask;
+  a.BN = BN; a.Cimg = Cimg; a.H = H; a.W = W; a.ds = downsample; a.mode = mode; a.nb = num_bins;
+  a.oH = (H - downsample / 2 + downsample - 1) / downsample;   // len(range(downsample // 2, H, downsample))
+  a.oW = (W - downsample / 2 + downsample - 1) / downsample;
+  GC_CHECK_ARG(a.oH >= 1 && a.oW >= 1, "image smaller than half the downsample factor");
+  a.dmin = d_min; a.dmax = d_max;
+  a.bin = mode == 0 ? (float)(((double)d_max - d_min) / num_bins) : (float)(2.0 * ((double)d_max - d_min) / ((double)num_bins * (1 + num_bins)));
+  const long long total = (long long)BN * a.oH * a.oW;
+  GC_CHECK_ARG((total + 255) / 256 < (1LL << 31), "too many pixels");
+  lss_depth_target_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(a);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_maxpool3x3s2_fwd(const float* x, float* y, int N, int C, int H, int W, void* stream) {
+  GC_CHECK_ARG(x && y, "null pointer");
+  GC_CHECK_ARG(N >= 1 && C >= 1 && H >= 1 && W >= 1, "bad dims");
+  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+  const long long total = (long long)N * C * Ho * Wo;
+  GC_CHECK_ARG((total + 255) / 256 < (1LL << 31), "tensor too large");
+  maxpool3x3s2_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, y, total, H, W, Ho, Wo);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
 }
 
 }  // extern "C"

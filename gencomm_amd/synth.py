@@ -85,6 +85,20 @@ def fill_params_(module, seed: int) -> None:
             p.copy_(torch.from_numpy(v).to(p.device, p.dtype))
 
 
+def fill_running_stats_(module, seed: int) -> None:
+    """Overwrite the running statistics of every BatchNorm of ``module`` in sorted-name order from one RandomState(seed) stream:
+    mean 0.1 N(0, 1), variance U(0.5, 1.5) -- an eval-mode fold that ignores either cannot pass parity."""
+    import torch
+
+    rng = np.random.RandomState(seed)
+    with torch.no_grad():
+        for name, m in sorted(module.named_modules(), key=lambda kv: kv[0]):
+            if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.running_mean is not None:
+                n = m.running_mean.numel()
+                m.running_mean.copy_(torch.from_numpy((0.1 * rng.standard_normal(n)).astype(np.float32)))
+                m.running_var.copy_(torch.from_numpy(rng.uniform(0.5, 1.5, n).astype(np.float32)))
+
+
 def make_pairwise_t_matrix(record_len: Sequence[int], max_cav: int, seed: int,
                            max_shift: float = 40.0) -> np.ndarray:
     """[B, L, L, 4, 4] float64; entry [b, i, j] maps agent i's frame into agent j's frame

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GENCOMM_ABI_VERSION 11
+#define GENCOMM_ABI_VERSION 12
 
 int gencomm_abi_version(void);
 const char* gencomm_last_error(void);
@@ -330,7 +330,8 @@ int gencomm_warp_attfuse_fwd(const float* x, const double* theta, const int* sce
  *          gencomm_conv2d_prepared_floats(Cin, Cout, KH, KW, transposed) floats (= Cin*Cout*KH*KW for the other shapes; -1: bad dims).
  * fold:    BatchNorm2d (eval) and/or conv bias -> per-channel scale/shift; pass NULL for the four BN tensors
  *          (and/or conv_bias) when absent.
- * fwd:     y[:, out_coff:out_coff+Cout] = act(conv(x) * scale + shift); supported: 3x3 stride 1|2 any pad, 1x1 stride 1;
+ * fwd:     y[:, out_coff:out_coff+Cout] = act(conv(x) * scale + shift); supported: 3x3 stride 1|2 any pad, 1x1 stride 1, 7x7 stride 2
+ *          any pad (the ResNet stem, ABI v12: exact fp32 MFMA);
  *          ups = s > 1 runs ConvTranspose2d(kernel = stride = s) (KH = KW = 1 on the prepared matrix, output H*s x W*s).
  *          KH = KW = 2 with ups = 2 (stride 1, pad 0; output 2H x 2W): the sub-pixel form of a TRANSPOSED 3x3 stride-2 pad-1 convolution,
  *          i.e. the input gradient of base_bev_backbone.py:57-63's stride-2 layers: GEMM row c*4 + a*2 + b = output channel c at
@@ -645,6 +646,32 @@ int gencomm_bnrow_train_bwd(const float* x, const float* y, const float* dy, con
 int gencomm_sp_rules_inv_fwd(const long long* in_keys, int n_in, const long long* out_keys, int n_out, int B, const int* in_dims3,
                              const int* kernel3, const int* stride3, const int* pad3, int* inv, void* stream);
 int gencomm_sp_wgrad(const float* x, const float* dy, const int* nbr, float* dw, int n_out, int K, int Cin, int Cout, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Lift-Splat-Shoot camera encoder, ABI v12 (opencood/models/heter_encoders.py:83-241, sub_modules/lss_submodule.py:140-233,
+ * utils/camera_utils.py:129-246). B agents x N cameras, D depth bins, an fH x fW feature map per camera, C image channels;
+ * grid: lo3 = bx - dx / 2, dx3, nx3 = cells along (x, y, z), all three HOST arrays (float32, as the reference's tensors).
+ *   gencomm_lss_splat_fwd   get_geometry + get_cam_feats' softmax / lift + voxel_pooling + QuickCumsum + griddify, without the
+ *                           lifted tensor: depth_logit [B N][D][fH][fW], feat [B N][C][fH][fW] (image_head output), frustum
+ *                           [D][fH][fW][3], rots / intrins / post_rots [B][N][3][3], trans / post_trans [B][N][3] (all device)
+ *                           -> out [B][nz C][ny][nx] (channel z C + c, every element written: empty cells are 0);
+ *                           cell [B N D fH fW] int32 (may be NULL): the reference's rank x (ny nz B) + y (nz B) + z B + b of each
+ *                           frustum point (cell coordinates truncated toward zero, as .long()), -1 outside the grid.
+ *                           Scratch: gencomm_lss_workspace_bytes. Three launches + the rocPRIM radix sort; deterministic.
+ *   gencomm_lss_depth_target_fwd  depth_gt_indices of depth_supervision (CamEncode*.get_gt_depth_dist, eval mode): channel 3 of
+ *                           imgs [BN][Cimg][H][W], clamp_max(d_max), bin_depths (mode 0 UD, 1 LID) picked at downsample / 2 ::
+ *                           downsample -> indices int64 [BN][oH][oW] (clamped into [0, num_bins)), mask uint8 (may be NULL): 1
+ *                           where the unclamped index was finite and inside [0, num_bins)
+ *   gencomm_maxpool3x3s2_fwd  nn.MaxPool2d(3, stride 2, padding 1) on [N][C][H][W] (the ResNet stem)
+ * -------------------------------------------------------------------------------------------- */
+long long gencomm_lss_workspace_bytes(int B, int N, int D, int fH, int fW, int C, const int* nx3);
+int gencomm_lss_splat_fwd(const float* depth_logit, const float* feat, const float* frustum, const float* rots, const float* trans,
+                          const float* intrins, const float* post_rots, const float* post_trans, const float* lo3, const float* dx3,
+                          const int* nx3, int B, int N, int D, int fH, int fW, int C, float* out, int* cell, void* workspace,
+                          long long workspace_bytes, void* stream);
+int gencomm_lss_depth_target_fwd(const float* imgs, int BN, int Cimg, int H, int W, int downsample, int mode, float d_min, float d_max,
+                                 int num_bins, long long* indices, unsigned char* mask, void* stream);
+int gencomm_maxpool3x3s2_fwd(const float* x, float* y, int N, int C, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }
