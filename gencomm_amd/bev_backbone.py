@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from . import _lib
 from .runtime import conv2d_prepare, f32c, ptr, require_gpu, stream_ptr
+from .train_ops import bn_batch_statistics
 
 
 def _versions(*tensors):
@@ -145,11 +146,12 @@ class _ConvBnTrainFn(torch.autograd.Function):
             y = torch.empty_like(pre)
             save = torch.empty(cout, 2, dtype=torch.float32, device=dev)
             scratch = pool_zeros(2 * cout, torch.float64, dev)
-            track = bn.track_running_stats and bn.running_mean is not None
+            T.check_batch_size(n * Ho * Wo, pre.shape)
+            track, momentum, nbt = T.bn_train_update(bn)         # _fusable: momentum set, the counter (if any) on the device
             b = conv.bias.detach().contiguous() if conv.bias is not None else None
             _lib.check(l.gencomm_convbn_train_fwd(ptr(x), ptr(w), ptr(b), ptr(unit[0]), ptr(unit[1]), ptr(bn.weight.detach()), ptr(bn.bias.detach()),
                                                   ptr(bn.running_mean) if track else 0, ptr(bn.running_var) if track else 0,
-                                                  ptr(bn.num_batches_tracked) if track else 0, float(bn.momentum), float(bn.eps), int(relu),
+                                                  ptr(nbt), momentum, float(bn.eps), int(relu),
                                                   ptr(prepared), ptr(pre), ptr(y), ptr(save), ptr(scratch), n, cin, H, W, cout, k, st_, p,
                                                   stream_ptr(dev)), "gencomm_convbn_train_fwd")
             ctx.save_for_backward(x, pre, y, save)
@@ -263,13 +265,13 @@ def conv2d_hip(x: torch.Tensor, conv: nn.Module, bn: Optional[nn.BatchNorm2d] = 
         # `residual` is added to BN(conv(x)) and the ReLU (if any) comes AFTER the sum (ResNet BasicBlock, resblock.py:48-62)
         grad_path = torch.is_grad_enabled() and (x.requires_grad or residual.requires_grad or any(
             p is not None and p.requires_grad for p in (conv.weight, conv.bias) + ((bn.weight, bn.bias) if bn is not None else ())))
-        if grad_path or (bn is not None and bn.training) or out is not None:
+        if grad_path or (bn is not None and bn_batch_statistics(bn)) or out is not None:
             y = conv2d_hip(x, conv, bn, False, pad) + residual
             return torch.relu(y) if relu else y
     if torch.is_grad_enabled():
         params = [p for p in (conv.weight, conv.bias) + ((bn.weight, bn.bias) if bn is not None else ()) if p is not None]
         if x.requires_grad or any(p.requires_grad for p in params):
-            fn = _ConvBnTrainFn if (bn is not None and bn.training) else _Conv2dHipFn
+            fn = _ConvBnTrainFn if (bn is not None and bn_batch_statistics(bn)) else _Conv2dHipFn
             y = fn.apply(x, conv, bn, relu, pad, *params)
             if out is None:
                 return y
@@ -290,7 +292,7 @@ def conv2d_hip(x: torch.Tensor, conv: nn.Module, bn: Optional[nn.BatchNorm2d] = 
             raise NotImplementedError("grouped / dilated / anisotropic Conv2d is not supported")
         stride, ups, gkh, gkw = conv.stride[0], 1, kh, kw
         p = conv.padding[0] if pad is None else pad
-    if bn is not None and bn.training:   # batch statistics without gradients (e.g. a training-mode forward under no_grad)
+    if bn is not None and bn_batch_statistics(bn):   # batch statistics without gradients (e.g. a training-mode forward under no_grad)
         from . import train_ops as T
         y, _ = T.bn2d_train_fwd(conv2d_hip(x, conv, None, relu=False, pad=pad), bn, relu)
         if out is None:

@@ -336,7 +336,7 @@ int gencomm_bnrow_train_fwd(const float* x, const float* gamma, const float* bet
   GC_HIP(hipMemsetAsync(scratch, 0, (size_t)C * 2 * sizeof(double), st));
   const int slots = 256 / C;
   bnrow_stats_kernel<<<std::max(1, std::min((n + slots * 16 - 1) / (slots * 16), 512)), 256, 0, st>>>(x, scratch, n, C);
-  bn2d_finish_rows_kernel<<<(C + 63) / 64, 64, 0, st>>>(scratch, save, running_mean, running_var, momentum, eps, (long long)n, C);
+  bn2d_finish_rows_kernel<<<(C + 63) / 64, 64, 0, st>>>(x, scratch, save, running_mean, running_var, momentum, eps, (long long)n, C);
   const long long total = (long long)n * C;
   bnrow_apply_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(x, save, gamma, beta, y, total, C, relu);
   GC_HIP(hipGetLastError());

@@ -494,14 +494,16 @@ __global__ __launch_bounds__(256) void sp_dense_kernel(const float* __restrict__
 //   weight gradient  = dW[o][ci][co] += sum_j x[nbr[o][j]][ci] dy[j][co]: one workgroup per (offset, chunk of output sites),
 //                      rows staged through LDS, 16 accumulators per thread, f32 atomics at the end
 // =====================================================================================================================
-// per-channel sum / sum of squares over rows (f64 atomics): 256 threads = (256 / C) row slots x C channels, C in {16, 32, 64, 128}
+// per-channel sum / sum of squares of x - x[0][c] over rows (f64 atomics; the shift by row 0 keeps the variance free of cancellation under a
+// large common offset): 256 threads = (256 / C) row slots x C channels, C in {16, 32, 64, 128}
 __global__ __launch_bounds__(256) void bnrow_stats_kernel(const float* __restrict__ x, double* __restrict__ acc, int n, int C) {
   __shared__ double s_red[256][2];
   const int tid = threadIdx.x, c = tid % C, slot = tid / C, slots = 256 / C;
+  const double sh = x[c];
   double s = 0.0, q = 0.0;
   for (long long r = (long long)blockIdx.x * slots + slot; r < n; r += (long long)gridDim.x * slots) {
-    const float v = x[(size_t)r * C + c];
-    s += v; q += (double)v * v;
+    const double d = x[(size_t)r * C + c] - sh;
+    s += d; q += d * d;
   }
   s_red[tid][0] = s; s_red[tid][1] = q;
   __syncthreads();
@@ -511,12 +513,13 @@ __global__ __launch_bounds__(256) void bnrow_stats_kernel(const float* __restric
     atomicAdd(&acc[c * 2 + 1], q);
   }
 }
-__global__ void bn2d_finish_rows_kernel(const double* __restrict__ acc, float* __restrict__ save /*[C][2] mean, rstd*/, float* __restrict__ running_mean,
-                                        float* __restrict__ running_var, float momentum, float eps, long long count, int C) {
+__global__ void bn2d_finish_rows_kernel(const float* __restrict__ x, const double* __restrict__ acc, float* __restrict__ save /*[C][2] mean, rstd*/,
+                                        float* __restrict__ running_mean, float* __restrict__ running_var, float momentum, float eps, long long count, int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const double m = acc[c * 2] / (double)count;
-  const double var = fmax(acc[c * 2 + 1] / (double)count - m * m, 0.0);
+  const double dm = acc[c * 2] / (double)count;                      // mean of x - x[0][c] (bnrow_stats_kernel)
+  const double m = (double)x[c] + dm;
+  const double var = fmax(acc[c * 2 + 1] / (double)count - dm * dm, 0.0);
   save[c * 2] = (float)m;
   save[c * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
   if (running_mean != nullptr) {   // nn.BatchNorm1d: running_var takes the unbiased estimate

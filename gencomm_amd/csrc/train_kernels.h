@@ -1046,7 +1046,8 @@ inline size_t dcn_scatter_scratch_floats(int n, int C, int H, int W) {
 
 // ---- BatchNorm2d in TRAINING mode (batch statistics) for the conv stacks around the hot path -------------------------------
 // (base_bev_backbone.py:47-52: conv -> BatchNorm2d(eps 1e-3, momentum 0.01) -> ReLU; stage 1 of the reference trains them).
-//   bn2d_stats_kernel      per-channel sum / sum of squares over (n, HW) in f64 (grid: channel x chunks)
+//   bn2d_stats_kernel      per-channel sum / sum of squares of x - x[0][c][0] over (n, HW) in f64 (grid: channel x chunks); the shift by the
+//                          channel's first value keeps E[d^2] - E[d]^2 free of cancellation under a large common offset (1e3 + 1e-2 randn)
 //   (mean, rstd (biased variance) -> save[c][2] and the running statistics (UNBIASED variance) are formed inside bn2d_apply_kernel)
 //   bn2d_apply_kernel      y = act(gamma (x - mean) rstd + beta)
 //   bn2d_bwd_reduce_kernel sums of g and g xhat per channel (g = dy masked by y > 0 when the block has a ReLU)
@@ -1057,21 +1058,23 @@ template <int V>
 __global__ __launch_bounds__(256) void bn2d_stats_kernel(const float* __restrict__ x, double* __restrict__ acc /*[C][2]*/, int n, int C, int HW) {
   __shared__ double s_red[4][2];
   const int c = blockIdx.x, tid = threadIdx.x;
+  const double sh = x[(size_t)c * HW];
   double s = 0.0, q = 0.0;
   if (V == 4) {
     for (int b = 0; b < n; ++b) {
       const float* __restrict__ xp = x + ((size_t)b * C + c) * HW;
       for (int p = 4 * (blockIdx.y * 256 + tid); p < HW; p += gridDim.y * 1024) {
         const float4 v = *reinterpret_cast<const float4*>(xp + p);
-        s += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
-        q += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
+        const double d0 = v.x - sh, d1 = v.y - sh, d2 = v.z - sh, d3 = v.w - sh;
+        s += (d0 + d1) + (d2 + d3);
+        q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
       }
     }
   } else {
     for (long long i = (long long)blockIdx.y * 256 + tid; i < (long long)n * HW; i += (long long)gridDim.y * 256) {
       const int b = (int)(i / HW), p = (int)(i - (long long)b * HW);
-      const float v = x[((size_t)b * C + c) * HW + p];
-      s += v; q += (double)v * v;
+      const double d = x[((size_t)b * C + c) * HW + p] - sh;
+      s += d; q += d * d;
     }
   }
   for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
@@ -1089,8 +1092,9 @@ __global__ __launch_bounds__(256) void bn2d_apply_kernel(const float* __restrict
                                                          float* __restrict__ y, int C, int HW, int relu, long long* __restrict__ nbt = nullptr) {
   const int c = blockIdx.y, b = blockIdx.z, p = V * (blockIdx.x * 256 + threadIdx.x);
   if (nbt != nullptr && blockIdx.x == 0 && c == 0 && b == 0 && threadIdx.x == 0) *nbt += 1;   // num_batches_tracked (one writer per launch)
-  const double md = acc[c * 2] / (double)count;
-  const double var = fmax(acc[c * 2 + 1] / (double)count - md * md, 0.0);
+  const double dm = acc[c * 2] / (double)count;                      // mean of x - x[0][c][0] (bn2d_stats_kernel)
+  const double md = (double)x[(size_t)c * HW] + dm;
+  const double var = fmax(acc[c * 2 + 1] / (double)count - dm * dm, 0.0);
   const float mean = (float)md, k = (float)(1.0 / sqrt(var + (double)eps));
   if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) {
     save[c * 2] = mean;

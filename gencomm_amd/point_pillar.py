@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from . import _lib
 from .runtime import f32c, ptr, require_gpu, stream_ptr
+from .train_ops import bn_batch_statistics
 
 
 class PFNLayer(nn.Module):  # pillar_vfe.py:10-29
@@ -70,7 +71,8 @@ class _PillarNetFn(torch.autograd.Function):
         Cout = w.shape[0]
         pre = T.conv2d(x4, w[:, :, None, None], None, 0)                                       # [1, 64, 1, M P]
         bn = pfn.norm
-        if bn.training:
+        train = bn_batch_statistics(bn)
+        if train:
             y, save = T.bn2d_train_fwd(pre, bn, True)
         else:
             save = torch.stack([bn.running_mean.float(), torch.rsqrt(bn.running_var.float() + bn.eps)], 1).contiguous()
@@ -78,7 +80,7 @@ class _PillarNetFn(torch.autograd.Function):
         out = torch.empty(M, Cout, dtype=torch.float32, device=dev)
         arg = torch.empty(M, Cout, dtype=torch.uint8, device=dev)
         _lib.check(l.gencomm_slot_max_fwd(ptr(y), ptr(out), ptr(arg), Cout, M, P, stream_ptr(dev)), "gencomm_slot_max_fwd")
-        ctx.pfn, ctx.M, ctx.P, ctx.train = pfn, M, P, bn.training
+        ctx.pfn, ctx.M, ctx.P, ctx.train = pfn, M, P, train
         ctx.save_for_backward(x4, pre, y, save, arg)
         return out
 
@@ -111,7 +113,7 @@ class _PillarNetFusedFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feats, pfn, *params):
-        from .runtime import zeros as pool_zeros
+        from . import train_ops as T
         l, dev = _lib.lib(), feats.device
         M, P, F = feats.shape
         w = f32c(pfn.linear.weight.detach())
@@ -122,10 +124,10 @@ class _PillarNetFusedFn(torch.autograd.Function):
         arg = torch.empty(M, C, dtype=torch.uint8, device=dev)
         save = torch.empty(C, 2, dtype=torch.float32, device=dev)
         moments = torch.empty(_lib.check_size(l.gencomm_pfn_moment_doubles(F), "gencomm_pfn_moment_doubles"), dtype=torch.float64, device=dev)
-        track = bn.track_running_stats and bn.running_mean is not None
-        momentum = 0.0 if bn.momentum is None else float(bn.momentum)
+        T.check_batch_size(M * P, (M, C, P))
+        track, momentum, nbt = T.bn_train_update(bn)      # momentum None: 1 / counter; a counter off the device is counted on the host
         _lib.check(l.gencomm_pfn_train_fwd(ptr(feats), ptr(w), ptr(gamma), ptr(beta), ptr(bn.running_mean) if track else 0, ptr(bn.running_var) if track else 0,
-                                           ptr(bn.num_batches_tracked) if track and bn.num_batches_tracked is not None else 0, momentum, float(bn.eps),
+                                           ptr(nbt), momentum, float(bn.eps),
                                            ptr(out), ptr(arg), ptr(save), ptr(moments), M, P, F, C, stream_ptr(dev)), "gencomm_pfn_train_fwd")
         ctx.pfn = pfn
         ctx.save_for_backward(feats, w, gamma, beta, save, moments, arg)
@@ -190,7 +192,7 @@ class PointPillar(nn.Module):
             feats = torch.cat([vf, f_cluster, f_center], dim=-1) * mask                     # [M, P, 10]
             M, P, F = feats.shape
         cout = pfn.linear.weight.shape[0]
-        if pfn.norm.training and F in (9, 10, 11) and cout in (32, 64, 128, 256) and P <= 255 and M > 0 and self.fused_train_pfn:
+        if bn_batch_statistics(pfn.norm) and F in (9, 10, 11) and cout in (32, 64, 128, 256) and P <= 255 and M > 0 and self.fused_train_pfn:
             pillar = _PillarNetFusedFn.apply(feats.contiguous(), pfn, pfn.linear.weight, pfn.norm.weight, pfn.norm.bias)   # [M, 64]
         else:
             x4 = feats.permute(2, 0, 1).reshape(1, F, 1, M * P).contiguous()               # channel-major point slots
@@ -205,7 +207,7 @@ class PointPillar(nn.Module):
         self._check_supported()
         require_gpu(voxel_features, "PointPillar.forward")
         pfn0 = self.pillar_vfe.pfn_layers[0]
-        if pfn0.norm.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
+        if bn_batch_statistics(pfn0.norm) or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             if batch_size is None:
                 batch_size = int(voxel_coords[:, 0].max().item()) + 1 if voxel_features.shape[0] > 0 else 1
             return self._encode_train(voxel_features.float(), voxel_coords, voxel_num_points, batch_size)

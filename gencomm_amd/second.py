@@ -22,6 +22,7 @@ from torch import nn
 
 from . import _lib
 from .runtime import f32c, ptr, require_gpu, stream_ptr, workspaces
+from .train_ops import bn_batch_statistics, check_batch_size
 
 
 TRACE = None  # tools/second_bench.py sets a list here to collect (Cin, Cout, rulebook) per layer for the FLOP count
@@ -165,7 +166,7 @@ def sparse_conv_bn_relu(x: SparseTensor, conv: _SparseConvBase, bn: nn.BatchNorm
     if TRACE is not None:
         TRACE.append((conv.in_channels, conv.out_channels, nbr))
     needs_grad = torch.is_grad_enabled() and (x.features.requires_grad or any(p.requires_grad for p in (conv.weight, bn.weight, bn.bias)))
-    if bn.training or needs_grad:
+    if bn_batch_statistics(bn) or needs_grad:
         out.features = _SparseLayerFn.apply(x.features, conv, bn, relu, (x, out, nbr), conv.weight, bn.weight, bn.bias)
         return out
     prep, ss = conv.prepared(bn, dev)
@@ -205,9 +206,11 @@ class _SparseLayerFn(torch.autograd.Function):
         pre = _raw_conv(feat, nbr, n_out, conv.weight, K, cin, cout, 0, dev)
         y = torch.empty_like(pre)
         save = torch.empty(cout, 2, dtype=torch.float32, device=dev)
-        if bn.training:
+        train = bn_batch_statistics(bn)
+        if train:
             scratch = torch.empty(2 * cout, dtype=torch.float64, device=dev)
-            track = bn.track_running_stats and bn.running_mean is not None
+            check_batch_size(n_out, (n_out, cout))
+            track = bn.training and bn.track_running_stats and bn.running_mean is not None
             momentum = 0.0 if bn.momentum is None else float(bn.momentum)
             if track:
                 bn.num_batches_tracked += 1
@@ -222,7 +225,7 @@ class _SparseLayerFn(torch.autograd.Function):
             save[:, 1] = torch.rsqrt(bn.running_var.float() + bn.eps)
             v = (pre - save[:, 0]) * save[:, 1] * bn.weight.detach().float() + bn.bias.detach().float()
             y = torch.relu(v) if relu else v
-        ctx.conv, ctx.bn, ctx.relu, ctx.info, ctx.train = conv, bn, relu, info, bn.training
+        ctx.conv, ctx.bn, ctx.relu, ctx.info, ctx.train = conv, bn, relu, info, train
         ctx.save_for_backward(feat, pre, y, save)
         return y
 

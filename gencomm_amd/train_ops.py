@@ -158,25 +158,46 @@ def conv3x3_c16(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, transposed:
     return out
 
 
-def bn2d_train_fwd(x: torch.Tensor, bn, relu: bool):
-    """(y, save): BatchNorm2d with batch statistics (+ ReLU) on the HIP kernels; updates bn.running_mean / running_var /
-    num_batches_tracked exactly as nn.BatchNorm2d in training mode does."""
-    x = _c(x)
-    n, C, H, W = x.shape
-    y = torch.empty_like(x)
-    save = torch.empty(C, 2, dtype=torch.float32, device=x.device)
-    scratch = pool_zeros(2 * C, torch.float64, x.device)          # arrives zeroed (flag 4): no memset launch inside the call
-    track = bn.track_running_stats and bn.running_mean is not None
+def bn_batch_statistics(bn) -> bool:
+    """nn.modules.batchnorm._BatchNorm's rule: batch statistics in train mode, and in eval mode when there are no running statistics
+    (track_running_stats=False)."""
+    return bn.training or (bn.running_mean is None and bn.running_var is None)
+
+
+def check_batch_size(values_per_channel: int, shape) -> None:
+    """torch.nn.functional.batch_norm refuses batch statistics over a single value per channel (_verify_batch_size): so do the HIP paths."""
+    if values_per_channel == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(shape)}")
+
+
+def bn_train_update(bn):
+    """(track, momentum, nbt) for one batch-statistics step of `bn`, with nn.BatchNorm's bookkeeping: track = the running statistics are
+    updated (train mode with buffers); momentum = the factor handed to the kernel (momentum None: 1 / the counter AFTER this batch, a host
+    read); nbt = the int64 device counter the kernel increments itself (no launch of its own, ABI v9), or None when it was counted here."""
+    track = bn.training and bn.track_running_stats and bn.running_mean is not None
     momentum = 0.0 if bn.momentum is None else float(bn.momentum)
     nbt = None
     if track:
-        if bn.momentum is None:                                   # cumulative average: the factor is 1 / the counter AFTER this batch (a host read)
+        if bn.momentum is None:
             bn.num_batches_tracked += 1
             momentum = 1.0 / float(bn.num_batches_tracked)
         elif bn.num_batches_tracked is not None and bn.num_batches_tracked.is_cuda and bn.num_batches_tracked.dtype == torch.int64:
-            nbt = bn.num_batches_tracked                          # incremented inside the normalisation kernel (ABI v9): no launch of its own
+            nbt = bn.num_batches_tracked
         elif bn.num_batches_tracked is not None:
             bn.num_batches_tracked += 1
+    return track, momentum, nbt
+
+
+def bn2d_train_fwd(x: torch.Tensor, bn, relu: bool):
+    """(y, save): BatchNorm2d with batch statistics (+ ReLU) on the HIP kernels; updates bn.running_mean / running_var /
+    num_batches_tracked exactly as nn.BatchNorm2d in training mode does (eval mode without running statistics: batch statistics, no update)."""
+    x = _c(x)
+    n, C, H, W = x.shape
+    check_batch_size(n * H * W, x.shape)
+    y = torch.empty_like(x)
+    save = torch.empty(C, 2, dtype=torch.float32, device=x.device)
+    scratch = pool_zeros(2 * C, torch.float64, x.device)          # arrives zeroed (flag 4): no memset launch inside the call
+    track, momentum, nbt = bn_train_update(bn)
     _lib.check(_lib.lib().gencomm_bn2d_train_fwd(ptr(x), ptr(_c(bn.weight)), ptr(_c(bn.bias)), ptr(bn.running_mean) if track else None,
                                                  ptr(bn.running_var) if track else None, ptr(y), ptr(save), ptr(scratch), momentum, float(bn.eps),
                                                  int(relu) | 4, n, C, H * W, ptr(nbt), stream_ptr(x.device)), "gencomm_bn2d_train_fwd")
