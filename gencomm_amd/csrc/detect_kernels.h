@@ -41,16 +41,13 @@ __device__ __forceinline__ float limit_period_f(float val, float offset, float p
   return val - floorf(val / period + offset) * period;
 }
 
-// box7 of anchor i after direction fix -> 8 projected corners; returns false when a size / z filter rejects it
-__device__ __forceinline__ bool det_decode_one(const DetArgs& a, int i, float (&c)[8][3]) {
-  const int HW = a.H * a.W;
-  const int an = i % a.A, pix = i / a.A;
-  const float* __restrict__ ab = a.anchors + (size_t)i * 7;
+// delta_to_boxes3d of anchor `an` at pixel `pix` (regression channel 7 an + d); ab = that anchor's 7 values
+__device__ __forceinline__ void det_box7(const float* __restrict__ reg, const float* __restrict__ ab, int an, int pix, int HW,
+                                         float (&b)[7]) {
   float d[7];
 #pragma unroll
-  for (int k = 0; k < 7; ++k) d[k] = a.reg[(size_t)(an * 7 + k) * HW + pix];
+  for (int k = 0; k < 7; ++k) d[k] = reg[(size_t)(an * 7 + k) * HW + pix];
   const float diag = sqrtf(ab[4] * ab[4] + ab[5] * ab[5]);
-  float b[7];
   b[0] = d[0] * diag + ab[0];
   b[1] = d[1] * diag + ab[1];
   b[2] = d[2] * ab[3] + ab[2];
@@ -58,6 +55,43 @@ __device__ __forceinline__ bool det_decode_one(const DetArgs& a, int i, float (&
   b[4] = expf(d[4]) * ab[4];
   b[5] = expf(d[5]) * ab[5];
   b[6] = d[6] + ab[6];
+}
+
+struct BoxExtent { float xmin, xmax, ymin, ymax, zmin, zmax; };
+
+// boxes_to_corners_3d (-> u, unprojected) + project_box3d (-> c); returns the extents of c
+__device__ __forceinline__ BoxExtent det_corners(const float (&b)[7], int hwl, const float* __restrict__ T, float (&u)[8][3],
+                                                 float (&c)[8][3]) {
+  // boxes_to_corners_3d: (l, w, h) extents; 'hwl' stores them as [h, w, l]
+  const float ex = hwl ? b[5] : b[3], ey = b[4], ez = hwl ? b[3] : b[5];
+  const float cosa = cosf(b[6]), sina = sinf(b[6]);
+  const float sx[8] = {1, 1, -1, -1, 1, 1, -1, -1}, sy[8] = {-1, 1, 1, -1, -1, 1, 1, -1}, sz[8] = {-1, -1, -1, -1, 1, 1, 1, 1};
+  BoxExtent e{INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float px = ex * (sx[k] / 2.f), py = ey * (sy[k] / 2.f), pz = ez * (sz[k] / 2.f);
+    // row vector times [[cos, sin, 0], [-sin, cos, 0], [0, 0, 1]]
+    const float rx = px * cosa + py * (-sina) + pz * 0.f + b[0];
+    const float ry = px * sina + py * cosa + pz * 0.f + b[1];
+    const float rz = px * 0.f + py * 0.f + pz * 1.f + b[2];
+    u[k][0] = rx; u[k][1] = ry; u[k][2] = rz;
+    const float X = T[0] * rx + T[1] * ry + T[2] * rz + T[3];
+    const float Y = T[4] * rx + T[5] * ry + T[6] * rz + T[7];
+    const float Z = T[8] * rx + T[9] * ry + T[10] * rz + T[11];
+    c[k][0] = X; c[k][1] = Y; c[k][2] = Z;
+    e.xmin = fminf(e.xmin, X); e.xmax = fmaxf(e.xmax, X);
+    e.ymin = fminf(e.ymin, Y); e.ymax = fmaxf(e.ymax, Y);
+    e.zmin = fminf(e.zmin, Z); e.zmax = fmaxf(e.zmax, Z);
+  }
+  return e;
+}
+
+// box7 of anchor i after direction fix -> 8 projected corners; returns false when a size / z filter rejects it
+__device__ __forceinline__ bool det_decode_one(const DetArgs& a, int i, float (&c)[8][3]) {
+  const int HW = a.H * a.W;
+  const int an = i % a.A, pix = i / a.A;
+  float b[7];
+  det_box7(a.reg, a.anchors + (size_t)i * 7, an, pix, HW, b);
   if (a.dir != nullptr) {
     int label = 0;
     float best = a.dir[(size_t)(an * a.nb) * HW + pix];
@@ -70,30 +104,12 @@ __device__ __forceinline__ bool det_decode_one(const DetArgs& a, int i, float (&
     b[6] = rot + a.dir_offset + period * (float)label;
     b[6] = limit_period_f(b[6], 0.5f, (float)(2.0 * 3.14159265358979323846));
   }
-  // boxes_to_corners_3d: (l, w, h) extents; 'hwl' stores them as [h, w, l]
-  const float ex = a.hwl ? b[5] : b[3], ey = b[4], ez = a.hwl ? b[3] : b[5];
-  const float cosa = cosf(b[6]), sina = sinf(b[6]);
-  const float sx[8] = {1, 1, -1, -1, 1, 1, -1, -1}, sy[8] = {-1, 1, 1, -1, -1, 1, 1, -1}, sz[8] = {-1, -1, -1, -1, 1, 1, 1, 1};
-  float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY, zmin = INFINITY, zmax = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const float px = ex * (sx[k] / 2.f), py = ey * (sy[k] / 2.f), pz = ez * (sz[k] / 2.f);
-    // row vector times [[cos, sin, 0], [-sin, cos, 0], [0, 0, 1]]
-    const float rx = px * cosa + py * (-sina) + pz * 0.f + b[0];
-    const float ry = px * sina + py * cosa + pz * 0.f + b[1];
-    const float rz = px * 0.f + py * 0.f + pz * 1.f + b[2];
-    const float X = a.T[0] * rx + a.T[1] * ry + a.T[2] * rz + a.T[3];
-    const float Y = a.T[4] * rx + a.T[5] * ry + a.T[6] * rz + a.T[7];
-    const float Z = a.T[8] * rx + a.T[9] * ry + a.T[10] * rz + a.T[11];
-    c[k][0] = X; c[k][1] = Y; c[k][2] = Z;
-    xmin = fminf(xmin, X); xmax = fmaxf(xmax, X);
-    ymin = fminf(ymin, Y); ymax = fmaxf(ymax, Y);
-    zmin = fminf(zmin, Z); zmax = fmaxf(zmax, Z);
-  }
-  const float x_len = xmax - xmin, y_len = ymax - ymin;
+  float u[8][3];
+  const BoxExtent e = det_corners(b, a.hwl, a.T, u, c);
+  const float x_len = e.xmax - e.xmin, y_len = e.ymax - e.ymin;
   // remove_large_pred_bbx: its "z extent" is the y extent again and is used as a truth value (non-zero)
   const bool size_ok = x_len <= 6.f && y_len <= 6.f && y_len != 0.f;
-  const bool z_ok = zmin >= -3.f && zmax <= 1.f;
+  const bool z_ok = e.zmin >= -3.f && e.zmax <= 1.f;
   return size_ok && z_ok;
 }
 
@@ -173,6 +189,191 @@ __global__ __launch_bounds__(256) void det_emit_kernel(const DetArgs a) {
   for (int k = 0; k < 8; ++k) { dst[3 * k] = c[k][0]; dst[3 * k + 1] = c[k][1]; dst[3 * k + 2] = c[k][2]; }
   a.scores[slot] = s;
   a.anchor_idx[slot] = i;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Multi-class decoding (V2X-Real heads): VoxelPostprocessor.post_process_v2xreal, voxel_postprocessor.py:787-943.
+// All agents of a call (up to kDetMaxAgents) go through ONE flag / scan / emit sequence: the per-agent pointers and sizes
+// travel in the kernel arguments, and a workgroup covers 256 anchors of one agent.
+// ---------------------------------------------------------------------------------------------
+constexpr int kDetMaxAgents = 8;  // MAX_AGENTS_PER_SCENE of the Python package
+
+struct DetMcAgent {
+  const float* cls;      // [A*nc][H][W]   class k of anchor j in channel j*nc + k   (batch 1)
+  const float* reg;      // [7A][H][W]
+  const float* anchors;  // [H][W][A][7]   anchor j = class set * rotations + rotation
+  const float* T;        // [4][4] row-major, agent -> ego
+  int H, W;
+  int block0;            // first workgroup of this agent in the launch
+};
+
+struct DetMcArgs {
+  DetMcAgent ag[kDetMaxAgents];
+  int n_agents, A, nc, hwl, cap;
+  int append;                // 0: the launch starts the call (counters start at 0); 1: later chunk (counters are read)
+  float thr;
+  float* score_tmp;          // [nblocks*256] scratch: best sigmoid, or -1 at or below the threshold
+  unsigned char* label_tmp;  // [nblocks*256] scratch: its class (0-based)
+  int* block_count;          // [nblocks] scratch: candidates per workgroup
+  int* block_bad;            // [nblocks] scratch: of those, the ones the size / z filters reject
+  int* block_off;            // [nblocks] scratch
+  float* corners;            // [cap][8][3] projected   (appended at *count)
+  float* unprojected;        // [cap][8][3] or null
+  float* scores;             // [cap]
+  int* labels;               // [cap] 1-based class
+  int* count;                // device: candidates so far
+  int* violations;           // device: candidates so far that remove_large_pred_bbx_v2xreal / remove_bbx_abnormal_z_v2xreal reject
+};
+
+__device__ __forceinline__ int detmc_agent(const DetMcArgs& a) {
+  int k = 0;
+  while (k + 1 < a.n_agents && (int)blockIdx.x >= a.ag[k + 1].block0) ++k;
+  return k;
+}
+
+// max over the class sigmoids, not the logits: two classes saturated to 1.0 tie, and the first wins (torch.max)
+__device__ __forceinline__ float detmc_score(const DetMcArgs& a, const DetMcAgent& g, int i, int& label) {
+  const int HW = g.H * g.W;
+  const int an = i % a.A, pix = i / a.A;
+  const float* __restrict__ p = g.cls + (size_t)(an * a.nc) * HW + pix;
+  float best = 1.0f / (1.0f + expf(-p[0]));
+  label = 0;
+  for (int k = 1; k < a.nc; ++k) {
+    const float v = 1.0f / (1.0f + expf(-p[(size_t)k * HW]));
+    if (v > best) { best = v; label = k; }
+  }
+  return best;
+}
+
+// box of anchor i (no direction fix) -> unprojected and projected corners; false when remove_large_pred_bbx_v2xreal or
+// remove_bbx_abnormal_z_v2xreal (box_utils.py:1115-1166) would remove it
+__device__ __forceinline__ bool detmc_decode_one(const DetMcArgs& a, const DetMcAgent& g, int i, float (&u)[8][3], float (&c)[8][3]) {
+  const int an = i % a.A, pix = i / a.A;
+  float b[7];
+  det_box7(g.reg, g.anchors + (size_t)i * 7, an, pix, g.H * g.W, b);
+  const BoxExtent e = det_corners(b, a.hwl, g.T, u, c);
+  const float x_len = e.xmax - e.xmin, y_len = e.ymax - e.ymin;
+  // as in the single-class filter, the "z extent" is the y extent again, used as a truth value
+  const bool size_ok = x_len <= 100.f && y_len <= 100.f && y_len != 0.f;
+  const bool z_ok = e.zmin >= -100.f && e.zmax <= 100.f;
+  return size_ok && z_ok;
+}
+
+// pass 1: class max + score filter -> score_tmp / label_tmp; candidates and filter violations per workgroup
+__global__ __launch_bounds__(256) void detmc_flag_kernel(const DetMcArgs a) {
+  __shared__ int s_cnt[4], s_bad[4];
+  const DetMcAgent& g = a.ag[detmc_agent(a)];
+  const int n = g.H * g.W * a.A;
+  const int i = ((int)blockIdx.x - g.block0) * 256 + threadIdx.x;
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  float s = -1.f;
+  bool bad = false;
+  if (i < n) {
+    int label;
+    const float p = detmc_score(a, g, i, label);
+    if (p > a.thr) {
+      s = p;
+      float u[8][3], c[8][3];
+      bad = !detmc_decode_one(a, g, i, u, c);
+    }
+    a.score_tmp[t] = s;
+    a.label_tmp[t] = (unsigned char)label;
+  }
+  const unsigned long long m = __ballot(s >= 0.f), mb = __ballot(bad);
+  if ((threadIdx.x & 63) == 0) {
+    s_cnt[threadIdx.x >> 6] = __popcll(m);
+    s_bad[threadIdx.x >> 6] = __popcll(mb);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a.block_count[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    a.block_bad[blockIdx.x] = s_bad[0] + s_bad[1] + s_bad[2] + s_bad[3];
+  }
+}
+
+// pass 2 (single workgroup): exclusive scan of the workgroup counts from *count (0 for the first chunk of a call); sum of the
+// violations into *violations likewise
+__global__ __launch_bounds__(1024) void detmc_scan_kernel(const DetMcArgs a, int nblocks) {
+  __shared__ int s_part[1024];
+  __shared__ int s_base, s_bad;
+  if (threadIdx.x == 0) {
+    s_base = a.append ? *a.count : 0;
+    s_bad = a.append ? *a.violations : 0;
+  }
+  __syncthreads();
+  int bad = 0;
+  for (int b0 = 0; b0 < nblocks; b0 += 1024) {
+    const int i = b0 + threadIdx.x;
+    const int v = i < nblocks ? a.block_count[i] : 0;
+    bad += i < nblocks ? a.block_bad[i] : 0;
+    s_part[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {  // Hillis-Steele inclusive scan
+      const int t = threadIdx.x >= o ? s_part[threadIdx.x - o] : 0;
+      __syncthreads();
+      s_part[threadIdx.x] += t;
+      __syncthreads();
+    }
+    if (i < nblocks) a.block_off[i] = s_base + s_part[threadIdx.x] - v;
+    __syncthreads();
+    if (threadIdx.x == 0) s_base += s_part[1023];
+    __syncthreads();
+  }
+  if (bad) atomicAdd(&s_bad, bad);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    *a.count = s_base;
+    *a.violations = s_bad;
+  }
+}
+
+// pass 3: candidates in the order of the reference's masked_select over the concatenated agents (agent, pixel, class set,
+// rotation)
+__global__ __launch_bounds__(256) void detmc_emit_kernel(const DetMcArgs a) {
+  __shared__ int s_cnt[4];
+  const DetMcAgent& g = a.ag[detmc_agent(a)];
+  const int n = g.H * g.W * a.A;
+  const int i = ((int)blockIdx.x - g.block0) * 256 + threadIdx.x;
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const float s = i < n ? a.score_tmp[t] : -1.f;
+  const bool keep = s >= 0.f;
+  const unsigned long long m = __ballot(keep);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) s_cnt[wv] = __popcll(m);
+  __syncthreads();
+  int base = a.block_off[blockIdx.x];
+  for (int w = 0; w < wv; ++w) base += s_cnt[w];
+  if (!keep) return;
+  const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
+  if (slot >= a.cap) return;  // the host compares *count with cap and fails loudly
+  float u[8][3], c[8][3];
+  detmc_decode_one(a, g, i, u, c);
+  float* __restrict__ dst = a.corners + (size_t)slot * 24;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { dst[3 * k] = c[k][0]; dst[3 * k + 1] = c[k][1]; dst[3 * k + 2] = c[k][2]; }
+  if (a.unprojected != nullptr) {
+    float* __restrict__ du = a.unprojected + (size_t)slot * 24;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { du[3 * k] = u[k][0]; du[3 * k + 1] = u[k][1]; du[3 * k + 2] = u[k][2]; }
+  }
+  a.scores[slot] = s;
+  a.labels[slot] = (int)a.label_tmp[t] + 1;
+}
+
+// after nms_rotated: [score, label] rows and the unprojected corners of the kept candidates, through out_index
+__global__ __launch_bounds__(256) void detmc_gather_kernel(const int* __restrict__ out_index, const int* __restrict__ out_count,
+                                                          const float* __restrict__ out_scores, const int* __restrict__ labels,
+                                                          const float* __restrict__ unprojected, int cap, int top,
+                                                          float* __restrict__ score_labels, float* __restrict__ out_unprojected) {
+  const int m = min(*out_count, top);
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= m) return;
+  const int src = out_index[t];
+  if (src < 0 || src >= cap) return;
+  score_labels[2 * t] = out_scores[t];
+  score_labels[2 * t + 1] = (float)labels[src];
+  if (unprojected != nullptr)
+    for (int k = 0; k < 24; ++k) out_unprojected[(size_t)t * 24 + k] = unprojected[(size_t)src * 24 + k];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -385,6 +586,51 @@ inline int det_decode_enqueue(DetArgs a, void* workspace, hipStream_t st) {
   det_flag_kernel<<<nblocks, 256, 0, st>>>(a);
   det_scan_kernel<<<1, 1024, 0, st>>>(a.block_count, a.block_off, nblocks, a.count);
   det_emit_kernel<<<nblocks, 256, 0, st>>>(a);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+// workgroups of the largest chunk of kDetMaxAgents agents
+inline long long det_mc_max_chunk_blocks(const int* H, const int* W, int n_agents, int A) {
+  long long best = 0;
+  for (int c0 = 0; c0 < n_agents; c0 += kDetMaxAgents) {
+    long long nb = 0;
+    for (int k = c0; k < n_agents && k < c0 + kDetMaxAgents; ++k) nb += ((long long)H[k] * W[k] * A + 255) / 256;
+    best = nb > best ? nb : best;
+  }
+  return best;
+}
+inline long long det_mc_workspace_bytes(const int* H, const int* W, int n_agents, int A) {
+  const long long nb = det_mc_max_chunk_blocks(H, W, n_agents, A);
+  return align_up(nb * 256 * 4, 256) + align_up(nb * 256, 256) + 3 * align_up(nb * 4, 256);
+}
+
+// three launches per chunk of kDetMaxAgents agents (one chunk up to MAX_AGENTS_PER_SCENE), whatever the number of agents in it
+inline int det_mc_decode_enqueue(DetMcArgs a, const float* const* cls, const float* const* reg, const float* const* anchors,
+                                 const float* const* T, const int* H, const int* W, int n_agents, void* workspace, hipStream_t st) {
+  const long long nb_max = det_mc_max_chunk_blocks(H, W, n_agents, a.A);
+  char* ws = (char*)workspace;
+  a.score_tmp = (float*)ws;
+  ws += align_up(nb_max * 256 * 4, 256);
+  a.label_tmp = (unsigned char*)ws;
+  ws += align_up(nb_max * 256, 256);
+  a.block_count = (int*)ws;
+  a.block_bad = (int*)(ws + align_up(nb_max * 4, 256));
+  a.block_off = (int*)(ws + 2 * align_up(nb_max * 4, 256));
+  for (int c0 = 0; c0 < n_agents; c0 += kDetMaxAgents) {
+    const int na = n_agents - c0 < kDetMaxAgents ? n_agents - c0 : kDetMaxAgents;
+    int nblocks = 0;
+    for (int k = 0; k < na; ++k) {
+      const int j = c0 + k;
+      a.ag[k] = DetMcAgent{cls[j], reg[j], anchors[j], T[j], H[j], W[j], nblocks};
+      nblocks += (int)(((long long)H[j] * W[j] * a.A + 255) / 256);
+    }
+    a.n_agents = na;
+    a.append = c0 > 0;
+    detmc_flag_kernel<<<nblocks, 256, 0, st>>>(a);
+    detmc_scan_kernel<<<1, 1024, 0, st>>>(a, nblocks);
+    detmc_emit_kernel<<<nblocks, 256, 0, st>>>(a);
+  }
   GC_HIP(hipGetLastError());
   return GC_OK;
 }

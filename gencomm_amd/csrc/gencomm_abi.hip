@@ -1109,6 +1109,45 @@ int gencomm_nms_rotated_fwd(const float* corners, const float* scores, const int
 
 int gencomm_nms_max_candidates(void) { return kNmsMaxN; }
 
+long long gencomm_det_mc_workspace_bytes(const int* H, const int* W, int n_agents, int A) {
+  if (!H || !W || n_agents < 1 || A < 1) { fail(GC_ERR_ARG, "bad H/W/n_agents/A"); return -1; }
+  for (int k = 0; k < n_agents; ++k)
+    if (H[k] < 1 || W[k] < 1) { fail(GC_ERR_ARG, "bad H/W"); return -1; }
+  return det_mc_workspace_bytes(H, W, n_agents, A);
+}
+
+int gencomm_det_mc_decode_fwd(const float* const* cls_preds, const float* const* reg_preds, const float* const* anchors,
+                              const float* const* transformation_matrices, const int* H, const int* W, int n_agents, int A,
+                              int num_class, float score_threshold, int order_hwl, float* corners, float* unprojected,
+                              float* scores, int* labels, int* count, int* violations, int capacity, void* workspace,
+                              long long workspace_bytes, void* stream) {
+  GC_CHECK_ARG(cls_preds && reg_preds && anchors && transformation_matrices && H && W && corners && scores && labels && count &&
+               violations && workspace, "null pointer");
+  GC_CHECK_ARG(n_agents >= 1 && A >= 1 && num_class >= 1 && num_class <= 255 && capacity >= 1, "bad n_agents/A/num_class/capacity");
+  for (int k = 0; k < n_agents; ++k) {
+    GC_CHECK_ARG(cls_preds[k] && reg_preds[k] && anchors[k] && transformation_matrices[k], "null agent pointer");
+    GC_CHECK_ARG(H[k] >= 1 && W[k] >= 1, "bad H/W");
+    GC_CHECK_ARG((long long)H[k] * W[k] * A * num_class < (1LL << 31), "too many anchors");
+  }
+  if (det_mc_workspace_bytes(H, W, n_agents, A) > workspace_bytes) return fail(GC_ERR_ARG, "workspace too small (gencomm_det_mc_workspace_bytes)");
+  DetMcArgs a{};
+  a.A = A; a.nc = num_class; a.hwl = order_hwl; a.cap = capacity; a.thr = score_threshold;
+  a.corners = corners; a.unprojected = unprojected; a.scores = scores; a.labels = labels; a.count = count; a.violations = violations;
+  return det_mc_decode_enqueue(a, cls_preds, reg_preds, anchors, transformation_matrices, H, W, n_agents, workspace, (hipStream_t)stream);
+}
+
+int gencomm_det_mc_gather_fwd(const int* out_index, const int* out_count, const float* out_scores, const int* labels,
+                              const float* unprojected, int capacity, int top, float* score_labels, float* out_unprojected,
+                              void* stream) {
+  GC_CHECK_ARG(out_index && out_count && out_scores && labels && score_labels, "null pointer");
+  GC_CHECK_ARG((unprojected == nullptr) == (out_unprojected == nullptr), "unprojected and out_unprojected are given together");
+  GC_CHECK_ARG(capacity >= 1 && top >= 1 && top <= kNmsMaxTop, "bad capacity/top");
+  detmc_gather_kernel<<<(top + 255) / 256, 256, 0, (hipStream_t)stream>>>(out_index, out_count, out_scores, labels, unprojected,
+                                                                        capacity, top, score_labels, out_unprojected);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
 int gencomm_bbox_overlaps_fwd(const float* boxes, const float* query_boxes, float* overlaps, int N, int K, void* stream) {
   GC_CHECK_ARG(N >= 0 && K >= 0, "bad N/K");
   if (N == 0 || K == 0) return GC_OK;

@@ -223,6 +223,42 @@ def make_detection_maps(H: int, W: int, A: int, seed: int, n_obj: int = 60, num_
     return cls, reg, dirp
 
 
+def make_detection_maps_v2xreal(H: int, W: int, A: int, nc: int, seed: int, n_obj: int = 60, variant: str = "plain"):
+    """Synthetic multi-class head outputs for the V2X-Real tail (post_process_v2xreal): cls logits [1, A*nc, H, W] (class k of
+    anchor j in channel j*nc + k; background -5, `n_obj` 3x3 clusters of positives, mostly on the class of the anchor's set) and
+    reg deltas [1, 7A, H, W]. Every variant but "empty" also has one confident candidate lifted ~20 m in z (z delta 14: outside a
+    +-15 m z range, inside the +-100 m z filter). variant: "plain"; "saturate" (one anchor whose first two classes both saturate
+    to a sigmoid of 1.0, the second with the larger logit); "oversize" (one candidate with a length delta of 6, which breaks the
+    100 m size filter); "empty" (no logit above -3). float32, numpy-deterministic."""
+    r = np.random.RandomState(seed)
+    cls = (np.full((1, A * nc, H, W), -5.0) + r.normal(0, 0.3, (1, A * nc, H, W))).astype(np.float32)
+    reg = r.normal(0, 0.15, (1, 7 * A, H, W)).astype(np.float32)
+    if variant == "empty":
+        return cls, reg
+    per_set = max(A // nc, 1)
+    for _ in range(n_obj):
+        j, y, x = r.randint(A), r.randint(1, H - 1), r.randint(1, W - 1)
+        k = min(j // per_set, nc - 1) if r.rand() < 0.8 else r.randint(nc)
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                if r.rand() < 0.7:
+                    cls[0, j * nc + k, y + dy, x + dx] = r.uniform(-1.0, 3.0)
+    def interior():
+        return r.randint(A), r.randint(H // 4, 3 * H // 4), r.randint(W // 4, 3 * W // 4)
+    j, y, x = interior()
+    cls[0, j * nc, y, x] = 4.0
+    reg[0, 7 * j + 2, y, x] = 14.0
+    if variant == "saturate":
+        j, y, x = interior()
+        cls[0, j * nc, y, x] = 20.0
+        cls[0, j * nc + 1, y, x] = 30.0
+    elif variant == "oversize":
+        j, y, x = interior()
+        cls[0, j * nc, y, x] = 2.5
+        reg[0, 7 * j + 5, y, x] = 6.0
+    return cls, reg
+
+
 def make_loss_inputs(seed: int, B: int, H: int, W: int, A: int, C: int, pos_frac: float = 0.02):
     """Synthetic head maps and anchor labels for the training criterion (PointPillarGencommLoss): cls / reg / dir predictions
     [B, A | 7A | 2A, H, W], labels `pos_equal_one` / `neg_equal_one` [B, H, W, A] (a few percent positives, a "don't care" band

@@ -371,7 +371,18 @@ int gencomm_conv2d_act_res_fwd(const float* x, const float* prepared, const floa
  *   (float)iou > iou_threshold), then -- when keep_range6 != NULL -- mask_boxes_outside_range_numpy (:384-421, all 8
  *   corners inside, bounds inclusive). *n_candidates is a DEVICE int (at most gencomm_nms_max_candidates() are
  *   considered). Outputs in pick order; *out_count device int.
- * bbox_overlaps: opencood/utils/box_overlaps.pyx:17-57, (N,4) x (K,4) -> (N,K), bit-identical to the compiled source. */
+ * bbox_overlaps: opencood/utils/box_overlaps.pyx:17-57, (N,4) x (K,4) -> (N,K), bit-identical to the compiled source.
+ * det_mc_decode (multi-class heads, VoxelPostprocessor.post_process_v2xreal :787-943): all n_agents agents of a call in one
+ *   set of three launches per 8 agents. Per agent k (host arrays of device pointers / ints): cls [A*num_class][H][W] (class c
+ *   of anchor j in channel j*num_class + c), reg [7A][H][W], anchors [H][W][A][7] float32, transformation_matrix [16].
+ *   score, label = max over the class sigmoids (the first maximum wins), score > score_threshold, delta_to_boxes3d_v2xreal
+ *   (no direction fix), boxes_to_corners_3d + project_box3d. Candidates in agent, then anchor order from slot 0: corners
+ *   [capacity][8][3], unprojected [capacity][8][3] (may be NULL), scores, labels (1-based) [capacity]; *count (device) = all
+ *   candidates (entries beyond capacity are dropped but counted), *violations (device) = candidates that
+ *   remove_large_pred_bbx_v2xreal / remove_bbx_abnormal_z_v2xreal (box_utils.py:1115-1166) reject -- kept, not dropped:
+ *   the reference asserts there are none. Workspace: gencomm_det_mc_workspace_bytes (H, W: host arrays of n_agents).
+ * det_mc_gather: after gencomm_nms_rotated_fwd on (corners, scores, count), score_labels[t] = {out_scores[t],
+ *   labels[out_index[t]]} and out_unprojected[t] = unprojected[out_index[t]] (both NULL or neither) for t < *out_count. */
 long long gencomm_det_workspace_bytes(int H, int W, int A);
 long long gencomm_nms_workspace_bytes(void);
 int gencomm_nms_max_candidates(void);
@@ -383,6 +394,15 @@ int gencomm_nms_rotated_fwd(const float* corners, const float* scores, const int
                             const float* keep_range6, float* out_boxes, float* out_scores, int* out_index, int* out_count,
                             void* workspace, long long workspace_bytes, void* stream);
 int gencomm_bbox_overlaps_fwd(const float* boxes, const float* query_boxes, float* overlaps, int N, int K, void* stream);
+long long gencomm_det_mc_workspace_bytes(const int* H, const int* W, int n_agents, int A);
+int gencomm_det_mc_decode_fwd(const float* const* cls_preds, const float* const* reg_preds, const float* const* anchors,
+                              const float* const* transformation_matrices, const int* H, const int* W, int n_agents, int A,
+                              int num_class, float score_threshold, int order_hwl, float* corners, float* unprojected,
+                              float* scores, int* labels, int* count, int* violations, int capacity, void* workspace,
+                              long long workspace_bytes, void* stream);
+int gencomm_det_mc_gather_fwd(const int* out_index, const int* out_count, const float* out_scores, const int* labels,
+                              const float* unprojected, int capacity, int top, float* score_labels, float* out_unprojected,
+                              void* stream);
 
 /* MaxFusion.forward (opencood/models/fuse_modules/fusion_in_one.py:87-124): same warp, element-wise max over the
  * agents of a scene instead of the attention; arguments as gencomm_warp_attfuse_fwd. */
