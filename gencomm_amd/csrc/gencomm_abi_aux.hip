@@ -420,6 +420,21 @@ int gencomm_head_loss(const float* cls, const float* reg, const float* dir, cons
   return head_loss_enqueue(a, (hipStream_t)stream);
 }
 
+int gencomm_head_loss_mc(const float* cls, const float* reg, const void* labels, const void* targets, int dtype, unsigned* count, float* gcls,
+                         float* greg, double* sums, int B, int S, int K, int H, int W, double cls_weight, double reg_weight, void* stream) {
+  GC_CHECK_ARG(cls && reg && labels && targets && count && gcls && greg && sums, "null pointer");
+  GC_CHECK_ARG(dtype == 0 || dtype == 1, "bad dtype flag (0: float32, 1: float64 labels / targets)");
+  GC_CHECK_ARG(B >= 1 && S >= 1 && K >= 1 && K <= kLossMcMaxClasses && H >= 1 && W >= 1, "bad dims (B, S, H, W >= 1, 1 <= K <= 8)");
+  GC_CHECK_ARG((long long)H * W * S * 7 < (1LL << 31) && (long long)H * W * S * K < (1LL << 31) && B <= 65535, "map too large");
+  const hipStream_t st = (hipStream_t)stream;
+  if (dtype == 1) {
+    HeadLossMcArgs<double> a{cls, reg, (const double*)labels, (const double*)targets, count, gcls, greg, sums, B, S, K, H * W, cls_weight, reg_weight};
+    return head_loss_mc_enqueue(a, count, st);
+  }
+  HeadLossMcArgs<float> a{cls, reg, (const float*)labels, (const float*)targets, count, gcls, greg, sums, B, S, K, H * W, cls_weight, reg_weight};
+  return head_loss_mc_enqueue(a, count, st);
+}
+
 // ---- Lift-Splat-Shoot camera encoder ---------------------------------------------------------------------------------
 static int lss_geom(LssGeom& g, int B, int N, int D, int fH, int fW, int C, const float* lo3, const float* dx3, const int* nx3) {
   GC_CHECK_ARG(lo3 && dx3 && nx3, "null pointer");

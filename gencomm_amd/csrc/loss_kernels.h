@@ -131,4 +131,160 @@ inline int head_loss_enqueue(const HeadLossArgs& a, hipStream_t st) {
   return GC_OK;
 }
 
+
+// -------------------------------------------------------------------------------------------------------------------------------------
+// Multi-class detection-head terms of the V2X-Real criteria (opencood/loss/point_pillar_v2xreal_loss.py and its GenComm twin
+// point_pillar_v2xreal_gencomm_loss.py: forward :88-160, WeightedSmoothL1Loss :12-70, cls_loss_func :168-199, add_sin_difference
+// :221-233), forward values AND the gradients of conf_loss + reg_loss with respect to the head maps, in two launches: a per-sample count
+// of the positive slots, then the loss.
+//
+// Layouts: cls [B][S*K][H][W], reg [B][7S][H][W], labels [B][H][W][S], targets [B][H][W][S][7]; S = slots per location (rotations x
+// class blocks), K = classes. The logits of slot j are channels j*K .. j*K+K-1, its regression channels 7j .. 7j+6.
+// Per sample b: P_b = #{label > 0}; cls weight [label == 0 or label > 0] / max(P_b, 1), reg weight [label > 0] / max(P_b, 1) (float32,
+// :104-114). The one-hot target over the K logits comes from the label VALUE l (class l - 1; l = -1 is multiplied by `cared` first and is
+// background, :116-125). Focal loss with alpha 0.25 and gamma 2 (:78-79) in float32. Regression: smooth-L1 with beta = 1/9 and a strict
+// `<`, NaN targets replaced by the prediction (difference 0, gradient 0), in the targets' dtype T as the reference's type promotion
+// does (sin / cos of the float32 prediction rounded to float32, then promoted). Both sums are divided by B (psm.shape[0]).
+// One thread per (sample, slot j, pixel): consecutive threads walk the pixels of one channel (coalesced in the NCHW maps).
+// -------------------------------------------------------------------------------------------------------------------------------------
+constexpr int kLossMcMaxClasses = 8;
+
+template <typename T>
+__device__ __forceinline__ T wave_sum_t(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+template <typename T>
+struct HeadLossMcArgs {
+  const float *cls, *reg;
+  const T *lab, *tgt;
+  const unsigned* count;   // [B] positive slots per sample (head_loss_mc_count_kernel)
+  float *gcls, *greg;      // d (conf_loss + reg_loss) / d map, same layouts as cls / reg
+  double* sums;            // [3] += conf_loss, reg_loss, their sum; the caller zeroes it
+  int B, S, K, HW;
+  double cls_weight, reg_weight;
+};
+
+// count[b] += #{labels[b][..] > 0}: one vector atomic per workgroup into the caller-zeroed counter
+template <typename T>
+__global__ __launch_bounds__(256) void head_loss_mc_count_kernel(const T* __restrict__ lab, unsigned* __restrict__ count, int n) {
+  __shared__ unsigned s_cnt[4];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  unsigned c = 0;
+  for (int i = blockIdx.x * 256 + tid; i < n; i += gridDim.x * 256) c += lab[(size_t)b * n + i] > T(0) ? 1u : 0u;
+  c = wave_sum_t(c);
+  if ((tid & 63) == 0) s_cnt[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned tot = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    if (tot) atomicAdd(&count[b], tot);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void head_loss_mc_kernel(const HeadLossMcArgs<T> a) {
+  __shared__ float s_cls[4];
+  __shared__ T s_reg[4];
+  const int b = blockIdx.y, tid = threadIdx.x, S = a.S, K = a.K, HW = a.HW;
+  const float inv_bs = 1.0f / (float)a.B;
+  float l_cls = 0.f;
+  T l_reg = T(0);
+  const int i = blockIdx.x * 256 + tid;   // (slot j, pixel hw) of sample b
+  if (i < S * HW) {
+    const int j = i / HW, hw = i - j * HW;
+    const size_t slot = ((size_t)b * HW + hw) * S + j;   // index of the slot in labels / targets
+    const T l = a.lab[slot];
+    const bool positive = l > T(0), negative = l == T(0);
+    const float pos_norm = fmaxf((float)a.count[b], 1.0f);
+    const float w = ((negative ? 1.0f : 0.f) + (positive ? 1.0f : 0.f)) / pos_norm;
+    // ---- classification: sigmoid focal loss over the K logits of the slot (:168-199), one-hot of the label value
+    const int cls_idx = l >= T(0) && l <= T(K) ? (int)l - 1 : -1;   // -1: background (an ignored slot's weight is 0)
+    const float cw = (float)a.cls_weight * inv_bs;
+    for (int k = 0; k < K; ++k) {
+      const size_t e = ((size_t)b * S * K + (size_t)j * K + k) * HW + hw;
+      const float x = a.cls[e];
+      const float t = k == cls_idx ? 1.f : 0.f;
+      const float p = 1.0f / (1.0f + expf(-x));
+      const float aw = t * 0.25f + (1.f - t) * 0.75f;
+      const float pt = t * (1.f - p) + (1.f - t) * p;
+      const float ex = expf(-fabsf(x));
+      const float bce = fmaxf(x, 0.f) - x * t + log1pf(ex);
+      l_cls += aw * (pt * pt) * bce * w;
+      // clamp(min = 0) passes the gradient at 0, |x| does not
+      const float dbce = (x >= 0.f ? 1.f : 0.f) - t - (x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f)) * ex / (1.f + ex);
+      const float dpt = (1.f - 2.f * t) * p * (1.f - p);
+      a.gcls[e] = aw * (2.f * pt * dpt * bce + pt * pt * dbce) * w * cw;
+    }
+    // ---- regression: smooth-L1 (beta 1/9, strict <) on (x, y, z, h, w, l, sin-difference of the yaw), positives only
+    const T beta = T(1.0 / 9.0), half_beta = T(0.5 * (1.0 / 9.0));
+    const T rw = (T)((positive ? 1.0f : 0.f) / pos_norm);
+    const T gw = (T)a.reg_weight / (T)a.B * rw;   // d reg_loss / d (weighted smooth-L1 term), autograd's order
+#pragma unroll
+    for (int c = 0; c < 7; ++c) {
+      const size_t e = ((size_t)b * 7 * S + (size_t)j * 7 + c) * HW + hw;
+      const float pv = a.reg[e];
+      const T tv = a.tgt[slot * 7 + c];
+      float sp = 0.f, cp = 0.f;
+      T st = T(0), ct = T(0), d;   // d = encoded prediction - encoded target (NaN target: the prediction)
+      bool nan;
+      if (c == 6) {
+        // correctly rounded float32 sin / cos of the prediction (and T ones of the target): the reference's CPU float32 trig is
+        // within 1 ulp of these, no closer form is available to a GPU
+        double sd, cd;
+        sincos((double)pv, &sd, &cd);
+        sp = (float)sd;
+        cp = (float)cd;
+        sincos((double)tv, &sd, &cd);
+        st = (T)sd;
+        ct = (T)cd;
+        const T pe = (T)sp * ct, te = (T)cp * st;
+        nan = te != te;
+        d = pe - (nan ? pe : te);
+      } else {
+        nan = tv != tv;
+        d = (T)pv - (nan ? (T)pv : tv);
+      }
+      const T n = d < T(0) ? -d : d;
+      const bool lt = n < beta;
+      l_reg += (lt ? T(0.5) * (n * n) / beta : n - half_beta) * rw;
+      const T sgn = d > T(0) ? T(1) : (d < T(0) ? T(-1) : T(0));
+      const T gd = (lt ? gw / beta * T(0.5) * (T(2) * n) : gw) * sgn;   // d reg_loss / d d
+      float g;
+      if (nan) {
+        g = 0.f;   // where(isnan(target), input, target): the two paths cancel exactly
+      } else if (c == 6) {
+        // the reference's two float32 paths into the prediction, rounded as autograd rounds them (the sum cancels near |d| = 1)
+        g = __fadd_rn(__fmul_rn((float)(gd * ct), cp), __fmul_rn((float)(-gd * st), -sp));   // no contraction into an FMA
+      } else {
+        g = (float)gd;
+      }
+      a.greg[e] = g;
+    }
+  }
+  l_cls = wave_sum(l_cls);
+  l_reg = wave_sum_t(l_reg);
+  if ((tid & 63) == 0) { s_cls[tid >> 6] = l_cls; s_reg[tid >> 6] = l_reg; }
+  __syncthreads();
+  if (tid == 0) {
+    const double c = ((double)s_cls[0] + (double)s_cls[1] + (double)s_cls[2] + (double)s_cls[3]) * a.cls_weight / a.B;
+    const double r = ((double)s_reg[0] + (double)s_reg[1] + (double)s_reg[2] + (double)s_reg[3]) * a.reg_weight / a.B;
+    atomicAdd(&a.sums[0], c);
+    atomicAdd(&a.sums[1], r);
+    atomicAdd(&a.sums[2], c + r);   // their sum: the differentiable output of the host-side Function
+  }
+}
+
+template <typename T>
+inline int head_loss_mc_enqueue(const HeadLossMcArgs<T>& a, unsigned* count, hipStream_t st) {
+  const int n = a.HW * a.S;
+  const int cnt_blocks = (n + 255) / 256 < 64 ? (n + 255) / 256 : 64;   // grid-stride beyond 16 K slots per sample
+  head_loss_mc_count_kernel<T><<<dim3(cnt_blocks, a.B), 256, 0, st>>>(a.lab, count, n);
+  GC_HIP(hipGetLastError());
+  head_loss_mc_kernel<T><<<dim3((n + 255) / 256, a.B), 256, 0, st>>>(a);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
 }  // namespace gc

@@ -278,6 +278,47 @@ def make_loss_inputs(seed: int, B: int, H: int, W: int, A: int, C: int, pos_frac
             "pred_feature": (gt + r.normal(0, 0.3, gt.shape)).astype(f)}
 
 
+def make_loss_heads_v2xreal(seed: int, targets: np.ndarray, K: int):
+    """Head maps for the V2X-Real criteria on given regression targets [B, H, W, S, 7]: cls logits [B, S*K, H, W] (~N(-2, 1.5)) and
+    reg [B, 7S, H, W] = the targets (NaN read as 0) plus N(0, 0.2) noise on 70 % of the values, so that some regression differences
+    fall inside the smooth-L1 quadratic zone (|d| < 1/9) and most outside. float32, numpy-deterministic."""
+    r = np.random.RandomState(seed)
+    B, H, W, S, _ = targets.shape
+    cls = r.normal(-2, 1.5, (B, S * K, H, W)).astype(np.float32)
+    t = np.nan_to_num(targets, nan=0.0).reshape(B, H, W, 7 * S).transpose(0, 3, 1, 2)
+    reg = (t + r.normal(0, 0.2, t.shape) * (r.rand(*t.shape) < 0.7)).astype(np.float32)
+    return cls, reg
+
+
+def make_loss_inputs_v2xreal(seed: int, B: int, H: int, W: int, R: int, K: int, C: int = 8, pos_frac: float = 0.02,
+                             nan_frac: float = 0.0, dtype=np.float64, feature_hw=None):
+    """Synthetic inputs of the V2X-Real criteria (PointPillarV2XRealLoss / ...GenCommLoss) in the collate's layouts, S = R*K slots per
+    location (class block j // R, rotation j % R): labels `pos_equal_one` [B, H, W, S] (sparse positives carrying their block's class
+    value 1..K, an ignore band of -1, 0 elsewhere), `targets` [B, H, W, S, 7] (zero off the positives; deltas ~N(0, 0.4), yaw residuals
+    across the whole circle), with one of codes 0..5 of `nan_frac` of the positive and of the ignored slots set to NaN (a NaN yaw target
+    makes the reference's loss NaN: sin(p) * cos(NaN) is the prediction's encoding); the head maps of
+    make_loss_heads_v2xreal, and a `gt_feature` / `pred_feature` pair [B, C, *feature_hw (default H, W)] (float32).  Labels and
+    targets are `dtype` (float64 like the reference's collate)."""
+    r = np.random.RandomState(seed)
+    S = R * K
+    u = r.rand(B, H, W, S)
+    block = (np.arange(S) // R + 1).astype(np.float64)
+    labels = np.where(u < pos_frac, block, np.where(u < 3 * pos_frac, -1.0, 0.0))
+    targets = r.normal(0, 0.4, (B, H, W, S, 7))
+    targets[..., 6] = r.uniform(-np.pi, np.pi, (B, H, W, S))
+    targets *= (labels > 0)[..., None]
+    if nan_frac > 0:
+        for sel in (labels > 0, labels < 0):
+            idx = np.argwhere(sel)
+            pick = idx[r.rand(len(idx)) < nan_frac]
+            targets[tuple(pick.T) + (r.randint(0, 6, len(pick)),)] = np.nan
+    cls, reg = make_loss_heads_v2xreal(seed + 1, targets, K)
+    fh, fw = feature_hw if feature_hw is not None else (H, W)
+    gt = np.maximum(r.normal(0, 1, (B, C, fh, fw)), 0).astype(np.float32)
+    return {"cls_preds": cls, "reg_preds": reg, "pos_equal_one": labels.astype(dtype), "targets": targets.astype(dtype), "gt_feature": gt,
+            "pred_feature": (gt + r.normal(0, 0.3, gt.shape)).astype(np.float32)}
+
+
 def stage1_model_args(T: int = 3, lidar_range=(-102.4, -51.2, -3, 102.4, 51.2, 1), layer_nums=(3, 5, 8), C: int = 128) -> dict:
     """The `model.args` block of opv2v/GenComm_yamls/gencomm/stage1/m1_att.yaml (:93-166) as a dict: one lidar modality
     (PointPillars, 0.4 m pillars over `lidar_range` -> 512 x 256 grid by default), BaseBEVBackbone `layer_nums`, shrink to

@@ -603,6 +603,20 @@ int gencomm_head_loss(const float* cls, const float* reg, const float* dir, cons
                       float pos_cls_weight, float gamma, float alpha, float cls_weight, float sigma, float reg_weight, float dir_weight,
                       int batch_size, void* stream);
 
+/* Multi-class detection-head terms of the V2X-Real training criteria, forward and gradients, in two launches (a per-sample count of the
+ * positive slots, then the loss): opencood/loss/point_pillar_v2xreal_gencomm_loss.py:88-160 (and its stage-2 twin point_pillar_v2xreal_loss.py)
+ * with WeightedSmoothL1Loss :12-70, cls_loss_func :168-199, add_sin_difference :221-233; labels / targets as generate_label_v2xreal and
+ * collate_batch_v2xreal produce them (opencood/data_utils/post_processor/voxel_postprocessor.py:312-461, :622-656).
+ * cls [B][S*K][H][W], reg [B][7S][H][W] (float32, contiguous); labels [B][H][W][S] (values -1 ignore, 0 background, 1..K class),
+ * targets [B][H][W][S][7], both float32 (dtype 0) or float64 (dtype 1). S = slots per location, 1 <= K <= 8 classes; the logits of slot j are
+ * channels j*K .. j*K+K-1, its regression channels 7j .. 7j+6. Per sample, with P = #{label > 0}: sigmoid focal loss (alpha 0.25, gamma 2,
+ * float32) over the one-hot of the label value, weighted [label >= 0] / max(P, 1); smooth-L1 (beta 1/9, strict <, NaN targets ignored) on the
+ * sin-difference encoding, weighted [label > 0] / max(P, 1), in the targets' dtype. Both are divided by B and weighted by cls_weight / reg_weight.
+ * count [B] (unsigned, ZEROED BY THE CALLER) receives P; sums [3] (double, ZEROED BY THE CALLER) += conf_loss, reg_loss, their sum;
+ * gcls / greg = d (conf_loss + reg_loss) / d map, overwritten. */
+int gencomm_head_loss_mc(const float* cls, const float* reg, const void* labels, const void* targets, int dtype, unsigned* count, float* gcls,
+                         float* greg, double* sums, int B, int S, int K, int H, int W, double cls_weight, double reg_weight, void* stream);
+
 /* Training path of MessageExtractorv2's deformable 3x3 convolution (message_extractor_v2.py:78,:108; DCNv1, padding 1, one offset
  * group), split into its sampling half and its GEMM half so that the backward is GEMMs on the general kernels + one scatter:
  *   gencomm_dcn_sample_fwd   col[n][c * 9 + k][p] = bilinear sample of x[n][c] at tap k's displaced position (zero outside)
