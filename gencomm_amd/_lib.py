@@ -127,6 +127,9 @@ _SIGNATURES = {
     "gencomm_slot_max_bwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "gencomm_head_loss": (_i, [_p] * 10 + [_i] * 5 + [_p, C.c_double] + [C.c_float] * 7 + [_i, _p]),
     "gencomm_head_loss_mc": (_i, [_p] * 4 + [_i] + [_p] * 4 + [_i] * 5 + [C.c_double] * 2 + [_p]),
+    "gencomm_target_assign_workspace_bytes": (_ll, [_i, _i, _i]),
+    "gencomm_target_standup_fwd": (_i, [_p, _i, _i, _p, _p]),
+    "gencomm_target_assign_fwd": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _p] + [_i] * 6 + [_p, _p, _p, _i, _p, _ll, _p]),
     "gencomm_dcn_sample_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "gencomm_dcn_scatter_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "gencomm_dcn_scatter_scratch_floats": (_ll, [_i, _i, _i, _i]),

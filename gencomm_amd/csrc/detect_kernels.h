@@ -15,6 +15,7 @@
 // multiply-add contraction switched off, so that the same candidates cross the same thresholds.
 #pragma once
 #include "common.h"
+#include "box_overlap.h"
 
 namespace gc {
 
@@ -540,8 +541,8 @@ __global__ __launch_bounds__(1024) void nms_greedy_kernel(const NmsOutArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// bbox_overlaps (box_overlaps.pyx:17-57): precision follows the C Cython emits -- float differences, `+ 1.0` and the
-// area products in double, float variables for box_area / iw / ih / ua, float product and division at the end.
+// bbox_overlaps (box_overlaps.pyx:17-57): one thread per entry of the (N, K) matrix; the entry itself is box_overlap.h's, which the
+// target assignment (target_kernels.h) shares.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bbox_overlaps_kernel(const float* __restrict__ boxes, const float* __restrict__ query,
                                                            float* __restrict__ out, int N, int K) {
@@ -550,17 +551,7 @@ __global__ __launch_bounds__(256) void bbox_overlaps_kernel(const float* __restr
   const int n = (int)(t / K), k = (int)(t - (long long)n * K);
   const float* b = boxes + (size_t)n * 4;
   const float* q = query + (size_t)k * 4;
-  const float box_area = (float)(((double)(q[2] - q[0]) + 1.0) * ((double)(q[3] - q[1]) + 1.0));
-  float r = 0.f;
-  const float iw = (float)((double)(fminf(b[2], q[2]) - fmaxf(b[0], q[0])) + 1.0);
-  if (iw > 0) {
-    const float ih = (float)((double)(fminf(b[3], q[3]) - fmaxf(b[1], q[1])) + 1.0);
-    if (ih > 0) {
-      const float ua = (float)(((double)(b[2] - b[0]) + 1.0) * ((double)(b[3] - b[1]) + 1.0) + (double)box_area - (double)(iw * ih));
-      r = iw * ih / ua;
-    }
-  }
-  out[t] = r;
+  out[t] = bbox_overlap_one(b[0], b[1], b[2], b[3], q[0], q[1], q[2], q[3], bbox_query_area(q[0], q[1], q[2], q[3]));
 }
 
 #pragma clang fp contract(fast)

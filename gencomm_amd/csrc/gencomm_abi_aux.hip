@@ -1,5 +1,6 @@
 // Second translation unit of libgencomm_hip.so: iou3d_nms (reference extension semantics), the point-cloud voxeliser,
-// the V2X-ViT attention kernels, the sparse 3-D convolutions of the SECOND encoder and the Lift-Splat-Shoot camera encoder.
+// the V2X-ViT attention kernels, the sparse 3-D convolutions of the SECOND encoder, the Lift-Splat-Shoot camera encoder
+// and the training-time anchor target assignment.
 // Kept apart from gencomm_abi.hip so that the rocPRIM templates do not lengthen the hot path's compile.
 #include "../../include/gencomm_hip.h"
 
@@ -10,6 +11,7 @@
 #include "loss_kernels.h"
 #include "lss_kernels.h"
 #include "sparse_kernels.h"
+#include "target_kernels.h"
 #include "v2xvit_kernels.h"
 #include "voxel_kernels.h"
 
@@ -433,6 +435,49 @@ int gencomm_head_loss_mc(const float* cls, const float* reg, const void* labels,
   }
   HeadLossMcArgs<float> a{cls, reg, (const float*)labels, (const float*)targets, count, gcls, greg, sums, B, S, K, H * W, cls_weight, reg_weight};
   return head_loss_mc_enqueue(a, count, st);
+}
+
+// ---- anchor target assignment (generate_label / generate_label_v2xreal) ---------------------------------------------
+long long gencomm_target_assign_workspace_bytes(int B, int nc, int max_num) {
+  if (B < 1 || B > 65535 || nc < 1 || nc > kTargetMaxClasses || max_num < 1 || max_num > kTargetMaxBoxes) {
+    fail(GC_ERR_ARG, "bad B / nc / max_num (1 <= B <= 65535, 1 <= nc <= 8, 1 <= max_num <= 256)");
+    return -1;
+  }
+  return target_workspace_bytes(B, nc, max_num);
+}
+
+int gencomm_target_standup_fwd(const double* anchors, int n_anchors, int hwl, float* out, void* stream) {
+  GC_CHECK_ARG(anchors && out, "null pointer");
+  GC_CHECK_ARG(n_anchors >= 1 && (hwl == 0 || hwl == 1), "bad n_anchors / hwl");
+  target_standup_kernel<<<(unsigned)((n_anchors + 255) / 256), 256, 0, (hipStream_t)stream>>>(anchors, n_anchors, hwl, (float4*)out);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_target_assign_fwd(const void* boxes, int box_dtype, int box_width, const void* mask, int mask_dtype, const double* const* anchors,
+                              const float* const* standup, const double* pos_threshold, const double* neg_threshold, int B, int nc, int max_num,
+                              int n_anchors, int R, int multiclass, void* pos, void* neg, void* targets, int out_dtype, void* workspace,
+                              long long workspace_bytes, void* stream) {
+  GC_CHECK_ARG(boxes && mask && anchors && standup && pos_threshold && neg_threshold && pos && neg && targets && workspace, "null pointer");
+  GC_CHECK_ARG((box_dtype == 0 || box_dtype == 1) && (out_dtype == 0 || out_dtype == 1) && mask_dtype >= 0 && mask_dtype <= 4,
+               "bad dtype flag (boxes / outputs 0: float32, 1: float64; mask 0: float32, 1: float64, 2: int32, 3: int64, 4: uint8 / bool)");
+  GC_CHECK_ARG(box_width == 7 || box_width == 8, "box rows are 7 or 8 wide");
+  GC_CHECK_ARG(multiclass == 0 || (multiclass == 1 && box_width == 8), "the multi-class layout needs the class id in column 7");
+  GC_CHECK_ARG(multiclass == 1 || nc == 1, "the single-class layout has nc = 1");
+  const long long need = gencomm_target_assign_workspace_bytes(B, nc, max_num);
+  if (need < 0) return GC_ERR_ARG;
+  if (need > workspace_bytes) return fail(GC_ERR_WORKSPACE, "workspace too small (gencomm_target_assign_workspace_bytes)");
+  GC_CHECK_ARG(R >= 1 && n_anchors >= R && n_anchors % R == 0 && (long long)n_anchors * nc * 7 < (1LL << 31), "bad n_anchors / R");
+  TargetArgs a{};
+  a.boxes = boxes; a.mask = mask; a.pos = pos; a.neg = neg; a.targets = targets;
+  a.B = B; a.nc = nc; a.max_num = max_num; a.n = n_anchors; a.R = R; a.width = box_width; a.box_f64 = box_dtype; a.mask_dtype = mask_dtype;
+  a.multiclass = multiclass;
+  for (int k = 0; k < nc; ++k) {
+    GC_CHECK_ARG(anchors[k] && standup[k], "null anchor pointer");
+    a.anchors[k] = anchors[k]; a.standup[k] = (const float4*)standup[k];
+    a.pos_thr[k] = (float)pos_threshold[k]; a.neg_thr[k] = (float)neg_threshold[k];
+  }
+  return target_assign_enqueue(a, workspace, out_dtype, (hipStream_t)stream);
 }
 
 // ---- Lift-Splat-Shoot camera encoder ---------------------------------------------------------------------------------

@@ -17,7 +17,13 @@ channel j * nc + k), ``reg_preds`` 7 A; the result is ``(pred_box3d [M, 8, 3], s
 or ``(None, None)``. Class max over the sigmoids, score filter, decoding (no direction fix), corners, projection, the size / z
 checks, the class-agnostic rotated NMS and the x/y range mask run in the HIP library, every agent of a call in the same
 launches; the only host round trip reads the candidate, kept and filter-violation counts together.
-Not mirrored: the training-time target assignment (``generate_label``, ``generate_label_v2xreal``), ``iou_preds``.
+
+Training side (``generate_label`` :188-310, ``generate_label_v2xreal`` :312-463, ``collate_batch`` / ``collate_batch_v2xreal`` :577-655):
+``generate_label_batch(object_bbx_center [B, max_num, 7 | 8], object_bbx_mask [B, max_num], anchors)`` makes ``pos_equal_one``,
+``neg_equal_one`` and ``targets`` on the device from the boxes the batch already carries, every sample (and, for V2X-Real, every class)
+in two launches of the library (``gencomm_target_assign_fwd``, csrc/target_kernels.h); the anchors' stand-up boxes are prepared once
+per anchor array and device. ``generate_label`` / ``generate_label_v2xreal`` are the per-sample calls with the reference's keywords.
+Not mirrored: ``iou_preds``, ``generate_pos_region_ranges``.
 """
 from __future__ import annotations
 
@@ -29,6 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import GenCommHipError
 from .runtime import f32c, ptr, require_gpu, stream_ptr
 
 
@@ -39,6 +46,7 @@ class VoxelPostprocessor:
         self.anchor_num = self.params["anchor_args"]["num"]
         self._cache = {}
         self._anchor_cache = None
+        self._target_cache = []
         if class_names is not None:  # voxel_postprocessor.py:32-66
             cfg = anchor_params["anchor_args"]["anchor_generator_config"]
             self.order = anchor_params["order"]
@@ -291,6 +299,127 @@ class VoxelPostprocessor:
             raise AssertionError(f"{bad} of {n_cand} candidates fail remove_large_pred_bbx_v2xreal / remove_bbx_abnormal_z_v2xreal")
         boxes = buf["out_boxes"] if projection else buf["out_unprojected"]
         return boxes[:m].clone(), buf["score_labels"][:m].clone()
+
+
+    # ------------------------------------------------------------------ training-time target assignment
+    _MASK_DTYPES = {torch.float32: 0, torch.float64: 1, torch.int32: 2, torch.int64: 3, torch.uint8: 4, torch.bool: 4}
+
+    def _target_anchors(self, anchors, dev):
+        """Per class: the float64 anchors [H W R, 7] on `dev` and their float32 stand-up boxes (``gencomm_target_standup_fwd``), made once
+        per anchor array (or list of arrays) and device and kept while the same objects come back, as `_device_anchors_v2xreal` keeps its
+        upload; the arrays are treated as constants. Returns (anchor tensors, stand-up tensors, H, W, R)."""
+        parts = list(anchors) if isinstance(anchors, (list, tuple)) else [anchors]
+        for c in self._target_cache:
+            if c[1] == dev and len(c[0]) == len(parts) and all(x is y for x, y in zip(c[0], parts)):
+                return c[2]
+        l = _lib.lib()
+        a64, sup, shape = [], [], None
+        for x in parts:
+            t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+            if t.dim() != 4 or t.shape[-1] != 7:
+                raise ValueError(f"anchors: expected [H, W, A, 7] (per class for the multi-class heads), got {tuple(t.shape)}")
+            if shape is None:
+                shape = tuple(t.shape[:3])
+            elif tuple(t.shape[:3]) != shape:
+                raise ValueError("every class must have the same [H, W, R] anchor grid")
+            t = t.to(device=dev, dtype=torch.float64).contiguous().reshape(-1, 7)
+            s = torch.empty(t.shape[0], 4, dtype=torch.float32, device=dev)
+            _lib.check(l.gencomm_target_standup_fwd(ptr(t), t.shape[0], 1, ptr(s), stream_ptr(dev)), "gencomm_target_standup_fwd")
+            a64.append(t)
+            sup.append(s)
+        entry = (a64, sup) + shape
+        self._target_cache = [(parts, dev, entry)] + self._target_cache[:3]
+        return entry
+
+    def _assign_targets(self, boxes, mask, anchors, multiclass, dtype):
+        assert self.params["order"] == "hwl", "Currently Voxel only support hwl bbx order."
+        if not (torch.is_tensor(boxes) and torch.is_tensor(mask) and boxes.is_cuda and mask.is_cuda):
+            raise GenCommHipError("target assignment: gt_box_center and mask must be tensors on the GPU (there is no CPU fallback)")
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("dtype: torch.float32 or torch.float64")
+        dev = boxes.device
+        if mask.device != dev:
+            raise ValueError("boxes and mask must live on the same device")
+        if boxes.dtype not in (torch.float32, torch.float64):
+            boxes = boxes.to(torch.float64)
+        if mask.dtype not in self._MASK_DTYPES:
+            mask = mask.to(torch.float64)
+        boxes, mask = boxes.contiguous(), mask.contiguous()
+        if boxes.dim() != 3 or boxes.shape[2] not in (7, 8) or tuple(mask.shape) != tuple(boxes.shape[:2]):
+            raise ValueError(f"expected boxes [B, max_num, 7 | 8] and mask [B, max_num], got {tuple(boxes.shape)} / {tuple(mask.shape)}")
+        B, max_num, width = boxes.shape
+        a64, sup, H, W, R = self._target_anchors(anchors, dev)
+        nc = len(a64)
+        if multiclass:
+            if nc != len(self.anchor_class_names):
+                raise ValueError(f"{nc} anchor arrays for {len(self.anchor_class_names)} classes")
+            pos_thr = [float(self.matched_thresholds[n]) for n in self.anchor_class_names]
+            neg_thr = [float(self.unmatched_thresholds[n]) for n in self.anchor_class_names]
+        else:
+            if nc != 1:
+                raise ValueError("the single-class head takes one [H, W, A, 7] anchor array")
+            pos_thr = [float(self.params["target_args"]["pos_threshold"])]
+            neg_thr = [float(self.params["target_args"]["neg_threshold"])]
+        l = _lib.lib()
+        key = ("target_ws", str(dev), B, nc, max_num)
+        if key not in self._cache:   # zeroed once here; every call leaves it zeroed
+            nbytes = _lib.check_size(l.gencomm_target_assign_workspace_bytes(B, nc, max_num), "gencomm_target_assign_workspace_bytes")
+            self._cache[key] = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        ws = self._cache[key]
+        S = nc * R
+        pos = torch.empty(B, H, W, S, dtype=dtype, device=dev)
+        neg = torch.empty(B, H, W, R, dtype=dtype, device=dev)
+        tgt = torch.empty((B, H, W, S, 7) if multiclass else (B, H, W, 7 * S), dtype=dtype, device=dev)
+        P, Dbl = ctypes.c_void_p * nc, ctypes.c_double * nc
+        _lib.check(l.gencomm_target_assign_fwd(
+            ptr(boxes), int(boxes.dtype == torch.float64), width, ptr(mask), self._MASK_DTYPES[mask.dtype],
+            P(*[ptr(t) for t in a64]), P(*[ptr(t) for t in sup]), Dbl(*pos_thr), Dbl(*neg_thr), B, nc, max_num, H * W * R, R,
+            int(multiclass), ptr(pos), ptr(neg), ptr(tgt), int(dtype == torch.float64), ptr(ws), ws.numel(), stream_ptr(dev)),
+            "gencomm_target_assign_fwd")
+        return {"targets": tgt, "pos_equal_one": pos, "neg_equal_one": neg}
+
+    def generate_label_batch(self, object_bbx_center, object_bbx_mask, anchors, num_anchors_per_location=None, dtype=torch.float32):
+        """What ``collate_batch`` / ``collate_batch_v2xreal`` return for the B samples of a batch, made on the device:
+        ``generate_label_batch(batch['ego']['object_bbx_center'], batch['ego']['object_bbx_mask'], anchors)``. The V2X-Real layout
+        (label map [B, H, W, S], targets [B, H, W, S, 7], neg_equal_one [B, H, W, R] of the last class) is chosen when the post-processor
+        was built with ``class_names``; otherwise [B, H, W, A], [B, H, W, 7A], [B, H, W, A]."""
+        multiclass = hasattr(self, "anchor_class_names")
+        if multiclass and num_anchors_per_location is not None:
+            parts = list(anchors) if isinstance(anchors, (list, tuple)) else [anchors]
+            if [int(x.shape[2]) for x in parts] != [int(v) for v in num_anchors_per_location]:
+                raise ValueError("num_anchors_per_location does not match the anchor arrays")
+        return self._assign_targets(object_bbx_center, object_bbx_mask, anchors, multiclass, dtype)
+
+    def generate_label(self, **kwargs):
+        """generate_label(gt_box_center=[max_num, 7], anchors=[H, W, A, 7], mask=[max_num], dtype=torch.float32) -> pos_equal_one,
+        neg_equal_one [H, W, A] and targets [H, W, 7A] on the device (voxel_postprocessor.py:188-310)."""
+        assert self.params["order"] == "hwl", "Currently Voxel only support hwl bbx order."
+        gt, mask = kwargs["gt_box_center"], kwargs["mask"]
+        if torch.is_tensor(gt) and torch.is_tensor(mask):
+            gt, mask = gt[None], mask[None]
+        out = self._assign_targets(gt, mask, kwargs["anchors"], False, kwargs.get("dtype", torch.float32))
+        return {"pos_equal_one": out["pos_equal_one"][0], "neg_equal_one": out["neg_equal_one"][0], "targets": out["targets"][0]}
+
+    def generate_label_v2xreal(self, **kwargs):
+        """generate_label_v2xreal(gt_box_center=[max_num, 8], anchors=per-class [H, W, R, 7], num_anchors_per_location=, mask=[max_num],
+        dtype=torch.float32) -> the label map pos_equal_one [H, W, S], targets [H, W, S, 7], neg_equal_one [H, W, R] of the last class
+        (voxel_postprocessor.py:312-463)."""
+        assert self.params["order"] == "hwl", "Currently Voxel only support hwl bbx order."
+        gt, mask = kwargs["gt_box_center"], kwargs["mask"]
+        if torch.is_tensor(gt) and torch.is_tensor(mask):
+            gt, mask = gt[None], mask[None]
+        out = self.generate_label_batch(gt, mask, kwargs["anchors"], kwargs.get("num_anchors_per_location"), kwargs.get("dtype", torch.float32))
+        return {"pos_equal_one": out["pos_equal_one"][0], "targets": out["targets"][0], "neg_equal_one": out["neg_equal_one"][0]}
+
+    @staticmethod
+    def collate_batch(label_batch_list):
+        """Stack per-sample label dictionaries of tensors (voxel_postprocessor.py:577-619)."""
+        return {k: torch.stack([d[k] for d in label_batch_list]) for k in ("targets", "pos_equal_one", "neg_equal_one")}
+
+    @staticmethod
+    def collate_batch_v2xreal(label_batch_list):
+        """Stack per-sample label dictionaries of tensors (voxel_postprocessor.py:621-655)."""
+        return {k: torch.stack([d[k] for d in label_batch_list]) for k in ("targets", "pos_equal_one", "neg_equal_one")}
 
 
 def bbox_overlaps(boxes: torch.Tensor, query_boxes: torch.Tensor) -> torch.Tensor:

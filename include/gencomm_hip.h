@@ -617,6 +617,34 @@ int gencomm_head_loss(const float* cls, const float* reg, const float* dir, cons
 int gencomm_head_loss_mc(const float* cls, const float* reg, const void* labels, const void* targets, int dtype, unsigned* count, float* gcls,
                          float* greg, double* sums, int B, int S, int K, int H, int W, double cls_weight, double reg_weight, void* stream);
 
+/* Training-time anchor target assignment on the device (csrc/target_kernels.h), replacing the per-sample CPU assigner
+ * VoxelPostprocessor.generate_label (opencood/data_utils/post_processor/voxel_postprocessor.py:188-310) and generate_label_v2xreal
+ * (:312-463) with their helpers boxes_to_corners_3d / corner2d_to_standup_box (opencood/utils/box_utils.py:152-204, :225-248) and
+ * bbox_overlaps (opencood/utils/box_overlaps.pyx:17-57), and the stacking of collate_batch / collate_batch_v2xreal (:577-655): every sample
+ * of the batch and every class in TWO launches, the anchors x boxes IoU matrix is never stored.
+ *   standup: anchors [n_anchors][7] float64 (one class's [H][W][R][7] array) -> out [n_anchors][4] float32 stand-up boxes (x1, y1, x2, y2),
+ *            float32 corners as the reference forms them; hwl = 1 for order 'hwl'. Done once per anchor array, kept by the caller.
+ *   assign:  boxes [B][max_num][box_width] (box_dtype 0: float32, 1: float64; box_width 7, or 8 with the class id 1..nc in column 7),
+ *            mask [B][max_num] (mask_dtype 0: float32, 1: float64, 2: int32, 3: int64, 4: uint8 / bool; a box is valid where mask == 1);
+ *            anchors / standup: HOST arrays of nc DEVICE pointers (per class [n_anchors][7] float64 and its stand-up boxes),
+ *            pos_threshold / neg_threshold: HOST arrays of nc doubles (compared in float32, as numpy does); n_anchors = H W R per class,
+ *            R anchors per location and class; max_num <= 256, nc <= 8.
+ *            multiclass 0 (nc = 1, generate_label): pos / neg [B][H][W][R] = pos_equal_one / neg_equal_one, targets [B][H][W][7R]; the
+ *            deltas of a positive anchor read row j of the UNFILTERED boxes for the j-th valid box, as :279 does.
+ *            multiclass 1 (generate_label_v2xreal, box_width 8): the boxes of class k are those with mask == 1 and column 7 - 1 == k, in input
+ *            order; pos [B][H][W][nc R] = the label map (-1 ignore, 0 background, class id), slot k R + r; targets [B][H][W][nc R][7];
+ *            neg [B][H][W][R] = neg_equal_one of the LAST class (:460).
+ *            Outputs are float32 (out_dtype 0) or float64 (1), written completely (zeros included); the deltas are computed in float64
+ *            from the float64 anchors and rounded once.
+ *            workspace: gencomm_target_assign_workspace_bytes(B, nc, max_num) bytes, ZEROED ONCE by the caller when it is allocated;
+ *            every call leaves it zeroed for the next one (no memset per call). One call at a time per workspace. */
+long long gencomm_target_assign_workspace_bytes(int B, int nc, int max_num);
+int gencomm_target_standup_fwd(const double* anchors, int n_anchors, int hwl, float* out, void* stream);
+int gencomm_target_assign_fwd(const void* boxes, int box_dtype, int box_width, const void* mask, int mask_dtype, const double* const* anchors,
+                              const float* const* standup, const double* pos_threshold, const double* neg_threshold, int B, int nc, int max_num,
+                              int n_anchors, int R, int multiclass, void* pos, void* neg, void* targets, int out_dtype, void* workspace,
+                              long long workspace_bytes, void* stream);
+
 /* Training path of MessageExtractorv2's deformable 3x3 convolution (message_extractor_v2.py:78,:108; DCNv1, padding 1, one offset
  * group), split into its sampling half and its GEMM half so that the backward is GEMMs on the general kernels + one scatter:
  *   gencomm_dcn_sample_fwd   col[n][c * 9 + k][p] = bilinear sample of x[n][c] at tap k's displaced position (zero outside)
