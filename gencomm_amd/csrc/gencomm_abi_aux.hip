@@ -101,6 +101,7 @@ int gencomm_hgt_attn_fwd(const float* qkv, const int* scene_off, float* out, int
   hipStream_t st = (hipStream_t)stream;
   if ((long long)HW * heads * B >= 131072 && (dim_head == 16 || dim_head == 32)) {   // enough (pixel, head) threads to fill the machine: every value loaded once
     const dim3 gs((HW + 255) / 256, heads, B);
+    GC_KLOG("hgt_attn_stream_kernel");
     if (dim_head == 32) hgt_attn_stream_kernel<32><<<gs, 256, 0, st>>>(a);
     else hgt_attn_stream_kernel<16><<<gs, 256, 0, st>>>(a);
     GC_HIP(hipGetLastError());
@@ -111,6 +112,7 @@ int gencomm_hgt_attn_fwd(const float* qkv, const int* scene_off, float* out, int
   else if (dim_head == 16) hgt_attn_kernel<16><<<grid, 256, 0, st>>>(a);
   else if (dim_head == 8) hgt_attn_kernel<8><<<grid, 256, 0, st>>>(a);
   else return fail(GC_ERR_ARG, "hgt attention: dim_head must be 8, 16, 32 or 64");
+  GC_KLOG("hgt_attn_kernel");
   GC_HIP(hipGetLastError());
   return GC_OK;
 }
@@ -150,7 +152,7 @@ int gencomm_hgt_attn_bwd(const float* qkv, const int* scene_off, const float* do
   else if (dim_head == 64) hgt_attn_bwd_kernel<64><<<grid, 256, 0, st>>>(a);
   else if (dim_head == 16) hgt_attn_bwd_kernel<16><<<grid, 256, 0, st>>>(a);
   else if (dim_head == 8) hgt_attn_bwd_kernel<8><<<grid, 256, 0, st>>>(a);
-  else return fail(GC_ERR_ARG, "hgt attention: dim_head must be 16, 32 or 64");
+  else return fail(GC_ERR_ARG, "hgt attention: dim_head must be 8, 16, 32 or 64");
   GC_HIP(hipGetLastError());
   return GC_OK;
 }

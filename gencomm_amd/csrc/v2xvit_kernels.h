@@ -340,12 +340,20 @@ __global__ __launch_bounds__(512) void win_attn_mfma_kernel(const WinArgs a) {
     for (int r = 0; r < 16; ++r) op[(size_t)(32 * db + 8 * (r >> 2) + 4 * h + (r & 3)) * HW] = o[db][r] * rden;
 }
 
+// kernel log (gencomm_klog_start / _stop): which of the two forms a (window, dim_head) pair went to
+inline void win_attn_klog(const char* kernel, int dh, int ws) {
+  if (!klog_armed()) return;
+  char name[64];
+  snprintf(name, sizeof name, "%s<%d,%d>", kernel, dh, ws);
+  klog_note(name);
+}
 template <int DH, int WS>
 inline int win_attn_launch(const WinArgs& a, int n, hipStream_t st) {
   if constexpr (WS * WS >= 64 && DH % 32 == 0) {
     const size_t shm = ((size_t)2 * 256 * (DH + 1) + (2 * WS - 1) * (2 * WS - 1)) * sizeof(float);
     if (shm > 48 * 1024) GC_HIP(hipFuncSetAttribute((const void*)win_attn_mfma_kernel<DH, WS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     const int nwin_ = (a.H / WS) * (a.W / WS), wpb = 256 / (WS * WS);
+    win_attn_klog("win_attn_mfma_kernel", DH, WS);
     win_attn_mfma_kernel<DH, WS><<<dim3((nwin_ + wpb - 1) / wpb, a.heads, n), 512, shm, st>>>(a);
     GC_HIP(hipGetLastError());
     return GC_OK;
@@ -354,6 +362,7 @@ inline int win_attn_launch(const WinArgs& a, int n, hipStream_t st) {
   const size_t sh = ((size_t)2 * WPB * T * DH + (2 * WS - 1) * (2 * WS - 1)) * sizeof(float);
   if (sh > 48 * 1024) GC_HIP(hipFuncSetAttribute((const void*)win_attn_kernel<DH, WS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
   const int nwin = (a.H / WS) * (a.W / WS);
+  win_attn_klog("win_attn_kernel", DH, WS);
   win_attn_kernel<DH, WS><<<dim3((nwin + WPB - 1) / WPB, a.heads, n), 256, sh, st>>>(a);
   GC_HIP(hipGetLastError());
   return GC_OK;

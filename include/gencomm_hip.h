@@ -519,7 +519,11 @@ int gencomm_voxelize_fwd(const float* points, int n, int nfeat, const float* vox
  *   gencomm_warp_affine_fwd  warp_affine_simple: out[i] = bilinear sample of x[i] on the float64 affine grid theta[i] [2][3]
  *   gencomm_hgt_attn_fwd     qkv [n][3 heads dim_head][HW] (q | k | v blocks) -> out [n][heads dim_head][HW]: per pixel and head,
  *                            softmax attention across the agents of each scene (scene_off [B+1]); relation matrices folded into
- *                            the k / v projections by the caller (all agents have type 0 in GenComm's use)
+ *                            the k / v projections by the caller (all agents have type 0 in GenComm's use).
+ *                            dim_head 8, 16, 32 or 64. A scene holds 1..8 agents: scene_off lives on the device, so the host
+ *                            entry cannot check it, and gencomm_hgt_attn_fwd / _bwd leave the rows of `out` / `dqkv` that
+ *                            belong to a scene of more than 8 (or fewer than 1) agents UNTOUCHED, without an error. The
+ *                            caller checks the scene sizes (the Python modules do: MAX_AGENTS_PER_SCENE)
  *   gencomm_win_attn_fwd     per agent, head and window x window tile: softmax(q k^T / sqrt(dim_head) + pos[dy][dx]) v,
  *                            pos_embedding [2 window - 1][2 window - 1]
  * -------------------------------------------------------------------------------------------- */
