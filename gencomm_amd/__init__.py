@@ -8,7 +8,8 @@ Public surface mirrors the reference's plugin API:
     AttFusion(feature_dims)            opencood/models/fuse_modules/fusion_in_one.py:126
     regroup, normalize_pairwise_tfm    fusion_in_one.py:48, opencood/utils/transformation_utils.py:68
     MessageExtractorv2(in_ch, out_ch)  opencood/models/gencomm_modules/message_extractor_v2.py:109
-    LiftSplatShoot(args)               opencood/models/heter_encoders.py:83 (camera_encoder: Resnet101)
+    LiftSplatShoot(args)               opencood/models/heter_encoders.py:83 (camera_encoder: Resnet101; trainable=True trains it)
+    PointPillarDepthLoss(args)         opencood/loss/point_pillar_depth_loss.py:11 (loss.core_method: point_pillar_depth_loss)
 
 All compute runs in hand-written HIP kernels behind the C ABI of ``include/gencomm_hip.h``.
 """
@@ -17,6 +18,7 @@ from .enhancer import Enhancer
 from .fusion import AttFusion, normalize_pairwise_tfm, regroup
 from .lift_splat_shoot import LiftSplatShoot
 from .message_extractor import MessageExtractorv2
+from .point_pillar_depth_loss import PointPillarDepthLoss
 from .unet import DiffusionUNet
 
 
@@ -32,5 +34,5 @@ def set_denoise_dtype(dtype) -> None:
     _lib.check(_lib.lib().gencomm_set_mode(_lib.MODE_ARITH, value), "gencomm_set_mode")
 
 
-__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "MessageExtractorv2", "LiftSplatShoot", "regroup", "normalize_pairwise_tfm",
+__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "regroup", "normalize_pairwise_tfm",
            "set_denoise_dtype"]

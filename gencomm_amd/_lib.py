@@ -161,6 +161,12 @@ _SIGNATURES = {
     "gencomm_lss_splat_fwd": (_i, [_p] * 8 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_i)] + [_i] * 6 + [_p, _p, _p, _ll, _p]),
     "gencomm_lss_depth_target_fwd": (_i, [_p, _i, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _p, _p, _p]),
     "gencomm_maxpool3x3s2_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "gencomm_lss_splat_bwd_workspace_bytes": (_ll, [_i, _i, C.POINTER(_i)]),
+    "gencomm_lss_splat_bwd": (_i, [_p, _p, _ll, _p, C.POINTER(_i)] + [_i] * 6 + [_p, _p, _p, _ll, _p]),
+    "gencomm_maxpool3x3s2_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "gencomm_stem7x7_wgrad_scratch_floats": (_ll, [_i] * 5),
+    "gencomm_stem7x7_wgrad": (_i, [_p, _p, _p] + [_i] * 5 + [_p, _ll, _p]),
+    "gencomm_depth_focal_loss": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, _p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

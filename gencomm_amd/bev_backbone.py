@@ -49,7 +49,8 @@ def _wgrad_scratch_floats(n, cin, H, W, cout, k, pad):
 def _conv_backward(x, g, conv, pad, need_x):
     """(dx, {parameter: gradient}) of the bare convolution given d(conv output) on the HIP primitives: nn.Conv2d 1x1 / 3x3 with stride
     1 or 2 (stride 2: dy spread onto the stride-1 grid, then the stride-1 input-gradient kernel), nn.ConvTranspose2d with kernel ==
-    stride (pixel-unshuffled dy, 1x1 GEMMs). None when the layer is outside that set."""
+    stride (pixel-unshuffled dy, 1x1 GEMMs), and the weight gradient of the 7x7 stride-2 pad-3 ResNet stem (no input gradient: raises).
+    None when the layer is outside that set."""
     import torch.nn.functional as F
     from . import train_ops as T
     grads = {}
@@ -67,6 +68,15 @@ def _conv_backward(x, g, conv, pad, need_x):
             grads[conv.bias] = g.sum((0, 2, 3))
         dx = T.conv2d(gu, wm[:, :, None, None], None, 0) if need_x else None          # dx[ci] = sum_j W[ci][j] gu[j]
         return dx, grads
+    if (conv.kernel_size == (7, 7) and conv.stride == (2, 2) and (conv.padding[0] if pad is None else pad) == 3 and conv.padding[0] == conv.padding[1]
+            and conv.groups == 1 and conv.dilation == (1, 1) and conv.bias is None and conv.in_channels <= 3 and conv.out_channels % 64 == 0):
+        # the ResNet stem (7x7 stride 2 pad 3 on the images): weight gradient only -- the images need no gradient
+        if need_x:
+            raise NotImplementedError(f"input gradient of the 7x7 stride-2 pad-3 stem (Conv2d {conv.in_channels} -> {conv.out_channels}, kernel (7, 7), "
+                                      "stride (2, 2)) is not implemented: its input is the image")
+        if conv.weight.requires_grad:
+            grads[conv.weight] = T.stem7x7_wgrad(g, x, conv.out_channels)
+        return None, grads
     if conv.kernel_size not in ((1, 1), (3, 3)) or conv.stride not in ((1, 1), (2, 2)) or conv.groups != 1 or conv.dilation != (1, 1):
         return None
     k, st = conv.kernel_size[0], conv.stride[0]

@@ -575,4 +575,108 @@ int gencomm_maxpool3x3s2_fwd(const float* x, float* y, int N, int C, int H, int 
   return GC_OK;
 }
 
+
+// ---- training the camera encoder: lift-splat backward, max-pool backward, stem weight gradient, depth focal loss ------------------
+long long gencomm_lss_splat_bwd_workspace_bytes(int B, int C, const int* nx3) {
+  if (!(nx3 && B >= 1 && C >= 1 && nx3[0] >= 1 && nx3[1] >= 1 && nx3[2] >= 1 && (long long)B * nx3[0] * nx3[1] * nx3[2] < (1LL << 31) - 1)) {
+    fail(GC_ERR_ARG, "gencomm_lss_splat_bwd_workspace_bytes: bad B / C / grid");
+    return -1;
+  }
+  return (long long)align_up((size_t)B * nx3[0] * nx3[1] * nx3[2] * C * 4, 256);
+}
+
+int gencomm_lss_splat_bwd(const float* grad_out, const void* fwd_workspace, long long fwd_workspace_bytes, const int* cell, const int* nx3,
+                          int B, int N, int D, int fH, int fW, int C, float* d_depth_logit, float* d_feat, void* workspace,
+                          long long workspace_bytes, void* stream) {
+  const float lo[3] = {0.f, 0.f, 0.f}, dx[3] = {1.f, 1.f, 1.f};
+  LssGeom g{};
+  if (int rc = lss_geom(g, B, N, D, fH, fW, C, lo, dx, nx3)) return rc;
+  GC_CHECK_ARG(grad_out && fwd_workspace && cell && d_depth_logit && d_feat && workspace, "null pointer");
+  GC_CHECK_ARG(D <= kLssBwdMaxD, "the backward supports at most 256 depth bins");
+  GC_CHECK_ARG((long long)B * N <= 65535, "too many cameras");
+  const long long pixels = (long long)B * N * fH * fW, npts = pixels * D;
+  const LssWs w = lss_ws(npts, pixels, C, lss_sort_bits(g));
+  if ((long long)w.total > fwd_workspace_bytes) return fail(GC_ERR_WORKSPACE, "forward workspace too small (gencomm_lss_workspace_bytes)");
+  const long long need = gencomm_lss_splat_bwd_workspace_bytes(B, C, nx3);
+  if (need < 0) return GC_ERR_ARG;
+  if (need > workspace_bytes) return fail(GC_ERR_WORKSPACE, "workspace too small (gencomm_lss_splat_bwd_workspace_bytes)");
+  hipStream_t st = (hipStream_t)stream;
+  const int plane = g.ny * g.nx;
+  float* gT = reinterpret_cast<float*>(workspace);
+  GC_KLOG("lss_grad_rows_kernel");
+  lss_grad_rows_kernel<<<dim3((plane + 63) / 64, (C + 63) / 64, g.B * g.nz), 256, 0, st>>>(grad_out, gT, C, plane);
+  GC_HIP(hipGetLastError());
+  LssBwdArgs a{};
+  const char* fws = reinterpret_cast<const char*>(fwd_workspace);
+  a.gT = gT; a.prob = reinterpret_cast<const float*>(fws + w.prob); a.featT = reinterpret_cast<const float*>(fws + w.featT);
+  a.cell = cell; a.dlogit = d_depth_logit; a.dfeat = d_feat;
+  a.B = g.B; a.nx = g.nx; a.ny = g.ny; a.nz = g.nz; a.D = D; a.HW = fH * fW; a.C = C;
+  const size_t lds = (size_t)(D + kLssBwdCh) * kLssBwdPitch * sizeof(float);
+  GC_KLOG("lss_splat_bwd_kernel");
+  lss_splat_bwd_kernel<<<dim3((a.HW + kLssBwdPx - 1) / kLssBwdPx, B * N), 256, lds, st>>>(a);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx, int N, int C, int H, int W, void* stream) {
+  GC_CHECK_ARG(x && dy && dx, "null pointer");
+  GC_CHECK_ARG(N >= 1 && C >= 1 && H >= 1 && W >= 1, "bad dims");
+  GC_CHECK_ARG((long long)H * W < (1LL << 31), "map too large");
+  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+  const long long total = (long long)N * C * H * W;
+  GC_CHECK_ARG((total + 255) / 256 < (1LL << 31), "tensor too large");
+  maxpool3x3s2_bwd_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, dy, dx, total, H, W, Ho, Wo);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+static bool stem7x7_dims(int N, int Cin, int Hi, int Wi, int Cout, long long& P, int& Ho, int& Wo) {
+  if (!(N >= 1 && Cin >= 1 && Cin * 49 <= kStemTaps && Hi >= 1 && Wi >= 1 && Cout >= 64 && Cout % 64 == 0 && Cout / 64 <= 65535)) return false;
+  Ho = (Hi + 6 - 7) / 2 + 1; Wo = (Wi + 6 - 7) / 2 + 1;
+  P = (long long)N * Ho * Wo;
+  return P < (1LL << 31) - kStemPx * (long long)kStemMaxSplit && (long long)N * Cin * Hi * Wi < (1LL << 40);
+}
+long long gencomm_stem7x7_wgrad_scratch_floats(int N, int Cin, int Hi, int Wi, int Cout) {
+  long long P; int Ho, Wo;
+  if (!stem7x7_dims(N, Cin, Hi, Wi, Cout, P, Ho, Wo)) {
+    fail(GC_ERR_ARG, "gencomm_stem7x7_wgrad_scratch_floats: bad dims (Cin <= 3, Cout a multiple of 64)");
+    return -1;
+  }
+  return (long long)stem7x7_split(P) * Cout * Cin * 49;
+}
+int gencomm_stem7x7_wgrad(const float* dy, const float* x, float* dw, int N, int Cin, int Hi, int Wi, int Cout, float* scratch,
+                          long long scratch_floats, void* stream) {
+  GC_CHECK_ARG(dy && x && dw && scratch, "null pointer");
+  long long P; int Ho, Wo;
+  GC_CHECK_ARG(stem7x7_dims(N, Cin, Hi, Wi, Cout, P, Ho, Wo), "bad dims (7x7 stride 2 pad 3: Cin <= 3, Cout a multiple of 64)");
+  const int S = stem7x7_split(P);
+  GC_CHECK_ARG(scratch_floats >= (long long)S * Cout * Cin * 49, "scratch smaller than gencomm_stem7x7_wgrad_scratch_floats");
+  StemWgradArgs a{};
+  a.dy = dy; a.x = x; a.part = scratch; a.N = N; a.Cin = Cin; a.Hi = Hi; a.Wi = Wi; a.Cout = Cout; a.Ho = Ho; a.Wo = Wo; a.P = (int)P;
+  a.per = (int)(((P + S - 1) / S + kStemPx - 1) / kStemPx * kStemPx);
+  hipStream_t st = (hipStream_t)stream;
+  GC_KLOG("stem7x7_wgrad_kernel");
+  stem7x7_wgrad_kernel<<<dim3(S, Cout / 64), 256, 0, st>>>(a);
+  GC_HIP(hipGetLastError());
+  const int total = Cout * Cin * 49;
+  stem7x7_wgrad_reduce_kernel<<<(total + 255) / 256, 256, 0, st>>>(scratch, dw, S, total);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_depth_focal_loss(const float* depth_logit, const long long* target, float* grad, double* sum, int BN, int D, int H, int W,
+                             float alpha, float gamma, float scale, void* stream) {
+  GC_CHECK_ARG(depth_logit && target && grad && sum, "null pointer");
+  GC_CHECK_ARG(BN >= 1 && D >= 1 && H >= 1 && W >= 1 && (long long)H * W < (1LL << 31), "bad dims");
+  GC_CHECK_ARG(gamma >= 0.f, "gamma must not be negative");
+  DepthFocalArgs a{};
+  a.logit = depth_logit; a.target = target; a.grad = grad; a.sum = sum; a.D = D; a.HW = H * W; a.total = (long long)BN * H * W;
+  a.alpha = alpha; a.gamma = gamma; a.scale = scale;
+  GC_CHECK_ARG((a.total + 255) / 256 < (1LL << 31), "too many pixels");
+  depth_focal_loss_kernel<<<(unsigned)((a.total + 255) / 256), 256, 0, (hipStream_t)stream>>>(a);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
 }  // extern "C"
+

@@ -287,4 +287,59 @@ inline int head_loss_mc_enqueue(const HeadLossMcArgs<T>& a, unsigned* count, hip
   return GC_OK;
 }
 
+
+// -------------------------------------------------------------------------------------------------------------------------------------
+// Depth term of the camera criteria (opencood/loss/point_pillar_depth_loss.py:40-54 with FocalLoss :105-185, reduction "none", no
+// smoothing, no foreground mask): per pixel -alpha (1 - p_t)^gamma log p_t at the target bin t of softmax(logit) over the D bins,
+// `.mean() * weight`, and its gradient with respect to the logits, in one launch.  logit / grad [BN][D][HW], target int64 [BN][HW].
+// One thread per pixel (coalesced along hw).  1 - p_t is formed as sum_{d != t} e_d / sum_d e_d (no cancellation near p_t = 1);
+// d loss / d z_d = -alpha ([d == t] - p_d) ((1 - p_t)^gamma - gamma (1 - p_t)^(gamma - 1) p_t log p_t).  The value is accumulated in
+// float64 (sum += scale * block sum; the caller zeroes it), scale = weight / (BN HW).  A target outside [0, D) poisons the value and
+// its pixel's gradients with NaN (the reference's one_hot raises).
+// -------------------------------------------------------------------------------------------------------------------------------------
+struct DepthFocalArgs {
+  const float* logit;
+  const long long* target;
+  float* grad;
+  double* sum;
+  int D, HW;
+  long long total;
+  float alpha, gamma, scale;
+};
+
+__global__ __launch_bounds__(256) void depth_focal_loss_kernel(const DepthFocalArgs a) {
+  __shared__ double s_red[4];
+  const int tid = threadIdx.x;
+  const long long i = (long long)blockIdx.x * 256 + tid;
+  double loss = 0.0;
+  if (i < a.total) {
+    const int D = a.D, HW = a.HW;
+    const long long bn = i / HW;
+    const int hw = (int)(i - bn * HW);
+    const float* __restrict__ lg = a.logit + (size_t)bn * D * HW + hw;
+    float* __restrict__ gr = a.grad + (size_t)bn * D * HW + hw;
+    const long long t = a.target[i];
+    const bool ok = t >= 0 && t < D;
+    float m = -INFINITY;
+    for (int d = 0; d < D; ++d) m = fmaxf(m, lg[(size_t)d * HW]);
+    float s = 0.f, rest = 0.f, et = 0.f, zt = 0.f;
+    for (int d = 0; d < D; ++d) {
+      const float z = lg[(size_t)d * HW], e = expf(z - m);
+      s += e;
+      if (d == t) { et = e; zt = z; } else rest += e;
+    }
+    const float rs = 1.0f / s;
+    const float logp = (zt - m) - logf(s), pt = et * rs, q = rest * rs;
+    const float mod = a.gamma == 2.0f ? q * q : powf(q, a.gamma);
+    const float dmod = a.gamma == 2.0f ? 2.0f * q : (q > 0.f ? a.gamma * powf(q, a.gamma - 1.0f) : 0.f);
+    const float k = ok ? -a.alpha * (mod - dmod * pt * logp) * a.scale : NAN;
+    loss = ok ? (double)(-a.alpha * mod * logp) : (double)NAN;
+    for (int d = 0; d < D; ++d) gr[(size_t)d * HW] = k * (d == t ? q : -expf(lg[(size_t)d * HW] - m) * rs);
+  }
+  loss = wave_sum_t<double>(loss);
+  if ((tid & 63) == 0) s_red[tid >> 6] = loss;
+  __syncthreads();
+  if (tid == 0) atomicAdd(a.sum, (s_red[0] + s_red[1] + s_red[2] + s_red[3]) * (double)a.scale);
+}
+
 }  // namespace gc

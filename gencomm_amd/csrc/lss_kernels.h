@@ -14,6 +14,16 @@
 //                       table, no host synchronisation, no memset); a wave sums prob * featT row over the interval (lanes =
 //                       channels, 256-byte row reads), the tile is staged in LDS and stored as 256-byte runs of the channel-major
 //                       map.  Empty cells are written as zeros by the same stores.  Fixed summation order, no atomics.
+//
+// Backward (training the camera encoder, gencomm_lss_splat_bwd), pixel-driven -- no sort, no atomics, no memset:
+//   lss_grad_rows_kernel  grad_out [B][nz C][ny][nx] transposed once through LDS to cell-major rows gT [B][nz][ny][nx][C], so that
+//                         a frustum point reads the C gradient values of its cell as one contiguous row
+//   lss_splat_bwd_kernel  one wave per pixel (lanes = channels, the pixel's feature row in registers) walks the D depth bins with
+//                         four row reads in flight: dprob_d = <g_d, feat> (one DPP wave sum), dfeat += prob_d g_d in registers in the
+//                         order of d, then the softmax backward in the same wave; d_depth_logit and d_feat are staged in LDS per
+//                         workgroup (32 consecutive pixels of one camera) and stored along hw
+// and the two trunk gradients the general convolution autograd lacks: maxpool3x3s2_bwd_kernel (input-driven gather, the forward's
+// arg-max rule recomputed) and stem7x7_wgrad_kernel (+ its fixed-order reduction) for the 7x7 stride-2 pad-3 stem.
 #pragma once
 #include <rocprim/rocprim.hpp>
 
@@ -262,5 +272,232 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const float* __restri
   }
   y[i] = m;
 }
+
+// ---- backward of the lift-splat ---------------------------------------------------------------------------------------------------
+constexpr int kLssBwdPx = 32, kLssBwdPitch = kLssBwdPx + 1, kLssBwdCh = 128, kLssBwdMaxD = 256;
+
+// grad_out [B nz][C][plane] -> gT [B nz][plane][C], plane = ny nx.  grid (ceil(plane / 64), ceil(C / 64), B nz), block 256
+__global__ __launch_bounds__(256) void lss_grad_rows_kernel(const float* __restrict__ g, float* __restrict__ gT, int C, int plane) {
+  __shared__ float tile[64][65];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int p0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+  const size_t bz = blockIdx.z;
+  const int cn = min(64, C - c0), pn = min(64, plane - p0);
+  for (int c = wv; c < cn; c += 4)
+    if (lane < pn) tile[c][lane] = g[(bz * C + c0 + c) * plane + p0 + lane];
+  __syncthreads();
+  for (int r = wv; r < pn; r += 4)
+    if (lane < cn) gT[(bz * plane + p0 + r) * C + c0 + lane] = tile[lane][r];
+}
+
+struct LssBwdArgs {
+  const float *gT, *prob, *featT;   // [B][nz][ny][nx][C], [BN][D][HW], [BN][HW][C]
+  const int* cell;                  // [BN][D][HW]: the forward's rank of every frustum point, -1 outside the grid
+  float *dlogit, *dfeat;            // [BN][D][HW], [BN][C][HW]
+  int B, nx, ny, nz, D, HW, C;
+};
+
+// one point of the walk: dprob of bin `d` (lane 0 keeps it in LDS, summed over the channel chunks), dfeat accumulated in registers
+#define GC_LSS_BWD_POINT(GA, GB, PR, DD)                                        \
+  do {                                                                          \
+    const float dp__ = wave_total(fmaf((GA), fa, (GB) * fb));                   \
+    acc_a = fmaf((PR), (GA), acc_a);                                            \
+    acc_b = fmaf((PR), (GB), acc_b);                                            \
+    if (lane == 0) {                                                            \
+      float* q__ = dl + (DD) * kLssBwdPitch + px;                               \
+      *q__ = c0 == 0 ? dp__ : *q__ + dp__;                                      \
+    }                                                                           \
+  } while (0)
+
+// grid (ceil(HW / 32), BN), block 256, dynamic LDS (D + 128) * 33 floats: the workgroup owns 32 consecutive pixels of one camera,
+// wave w the pixels w, w + 4, ...
+__global__ __launch_bounds__(256) void lss_splat_bwd_kernel(const LssBwdArgs a) {
+  extern __shared__ float lss_bwd_smem[];
+  float* dl = lss_bwd_smem;                                // [D][33]: dprob, then d_depth_logit
+  float* ft = lss_bwd_smem + (size_t)a.D * kLssBwdPitch;   // [128][33]: d_feat of one channel chunk
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int bn = blockIdx.y, hw0 = blockIdx.x * kLssBwdPx;
+  const int D = a.D, HW = a.HW, C = a.C;
+  const int npx = min(kLssBwdPx, HW - hw0);
+  for (int c0 = 0; c0 < C; c0 += kLssBwdCh) {
+    const int ca = c0 + lane, cb = ca + 64;
+    const bool va = ca < C, vb = cb < C;
+    for (int px = wv; px < npx; px += 4) {
+      const int hw = hw0 + px;
+      const float* __restrict__ frow = a.featT + ((size_t)bn * HW + hw) * C;
+      const float fa = va ? frow[ca] : 0.f, fb = vb ? frow[cb] : 0.f;
+      float acc_a = 0.f, acc_b = 0.f;
+      for (int d0 = 0; d0 < D; d0 += 64) {
+        const int dn = min(64, D - d0);
+        // lane d: probability and gradient row of point (bn, d0 + d, hw)
+        float pl = 0.f;
+        int rl = -1;
+        if (lane < dn) {
+          const size_t pt = ((size_t)bn * D + d0 + lane) * HW + hw;
+          pl = a.prob[pt];
+          const int r = a.cell[pt];
+          if (r >= 0) {   // rank = ((x ny + y) nz + z) B + b -> row ((b nz + z) ny + y) nx + x
+            const int b = r % a.B, t = r / a.B, iz = t % a.nz, u = t / a.nz, iy = u % a.ny, ix = u / a.ny;
+            rl = ((b * a.nz + iz) * a.ny + iy) * a.nx + ix;
+          }
+        }
+        int d = 0;
+        for (; d + 4 <= dn; d += 4) {   // four independent row reads in flight per wave
+          int r[4];
+          float pr[4], ga[4], gb[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            r[j] = __builtin_amdgcn_readlane(rl, d + j);
+            pr[j] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pl), d + j));
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float* __restrict__ row = a.gT + (size_t)max(r[j], 0) * C;
+            ga[j] = (va && r[j] >= 0) ? row[ca] : 0.f;
+            gb[j] = (vb && r[j] >= 0) ? row[cb] : 0.f;
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) GC_LSS_BWD_POINT(ga[j], gb[j], pr[j], d0 + d + j);
+        }
+        for (; d < dn; ++d) {
+          const int r = __builtin_amdgcn_readlane(rl, d);
+          const float pr = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pl), d));
+          const float* __restrict__ row = a.gT + (size_t)max(r, 0) * C;
+          const float ga = (va && r >= 0) ? row[ca] : 0.f, gb = (vb && r >= 0) ? row[cb] : 0.f;
+          GC_LSS_BWD_POINT(ga, gb, pr, d0 + d);
+        }
+      }
+      ft[lane * kLssBwdPitch + px] = acc_a;
+      ft[(64 + lane) * kLssBwdPitch + px] = acc_b;
+    }
+    __syncthreads();
+    const int cn = min(kLssBwdCh, C - c0);
+    for (int i = tid; i < cn * kLssBwdPx; i += 256) {   // stores run along hw
+      const int c = i / kLssBwdPx, px = i % kLssBwdPx;
+      if (px < npx) a.dfeat[((size_t)bn * C + c0 + c) * HW + hw0 + px] = ft[c * kLssBwdPitch + px];
+    }
+    __syncthreads();
+  }
+  // softmax backward: dlogit_d = prob_d (dprob_d - sum_d' prob_d' dprob_d')
+  for (int px = wv; px < npx; px += 4) {
+    const float* __restrict__ pp = a.prob + (size_t)bn * D * HW + hw0 + px;
+    float s = 0.f;
+    for (int d = lane; d < D; d += 64) s = fmaf(pp[(size_t)d * HW], dl[d * kLssBwdPitch + px], s);
+    s = wave_total(s);
+    for (int d = lane; d < D; d += 64) dl[d * kLssBwdPitch + px] = pp[(size_t)d * HW] * (dl[d * kLssBwdPitch + px] - s);
+  }
+  __syncthreads();
+  for (int i = tid; i < D * kLssBwdPx; i += 256) {
+    const int d = i / kLssBwdPx, px = i % kLssBwdPx;
+    if (px < npx) a.dlogit[((size_t)bn * D + d) * HW + hw0 + px] = dl[d * kLssBwdPitch + px];
+  }
+}
+#undef GC_LSS_BWD_POINT
+
+// backward of maxpool3x3s2_kernel, input-driven: an input pixel lies in at most four windows; each window's arg-max is recomputed
+// with the forward's rule (first element in row-major window order for which v > m || isnan(v): torch's tie rule) and the dy of the
+// windows this pixel wins are summed in (oy, ox) order.  No atomics.
+__global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx,
+                                                               long long total, int H, int W, int Ho, int Wo) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int ix = (int)(i % W), iy = (int)((i / W) % H);
+  const long long nc = i / ((long long)W * H);
+  const float* __restrict__ xp = x + (size_t)nc * H * W;
+  const float* __restrict__ dyp = dy + (size_t)nc * Ho * Wo;
+  const int self = iy * W + ix;
+  float s = 0.f;
+  for (int oy = iy >> 1; oy <= ((iy + 1) >> 1); ++oy) {   // windows oy with 2 oy - 1 <= iy <= 2 oy + 1
+    if (oy >= Ho) continue;
+    for (int ox = ix >> 1; ox <= ((ix + 1) >> 1); ++ox) {
+      if (ox >= Wo) continue;
+      float m = -INFINITY;
+      int am = -1;
+      for (int ky = 0; ky < 3; ++ky) {
+        const int jy = oy * 2 - 1 + ky;
+        if (jy < 0 || jy >= H) continue;
+        for (int kx = 0; kx < 3; ++kx) {
+          const int jx = ox * 2 - 1 + kx;
+          if (jx < 0 || jx >= W) continue;
+          const float v = xp[(size_t)jy * W + jx];
+          if (am < 0 || v > m || isnan(v)) { m = v; am = jy * W + jx; }
+        }
+      }
+      if (am == self) s += dyp[(size_t)oy * Wo + ox];
+    }
+  }
+  dx[i] = s;
+}
+
+// weight gradient of the 7x7 stride-2 pad-3 stem (Cin <= 3): dw [Cout][Cin 49] = dy [Cout x P] . patches [P x Cin 49], P = N Ho Wo.
+// Split over P: workgroup (s, g) sums its pixel range for output channels 64 g .. 64 g + 63 (lane = channel, wave q = taps 40 q ..
+// 40 q + 39, patches read from LDS as broadcast float4) into part [S][Cout][Cin 49]; stem7x7_wgrad_reduce_kernel adds the S
+// partial sums in order.  No atomics.
+constexpr int kStemTaps = 160, kStemPx = 32, kStemMaxSplit = 512;
+struct StemWgradArgs {
+  const float *dy, *x;
+  float* part;
+  int N, Cin, Hi, Wi, Cout, Ho, Wo, P, per;   // per: pixels per workgroup, a multiple of 32
+};
+__global__ __launch_bounds__(256) void stem7x7_wgrad_kernel(const StemWgradArgs a) {
+  __shared__ __attribute__((aligned(16))) float xs[kStemPx][kStemTaps];
+  __shared__ float dys[kStemPx][65];
+  const int tid = threadIdx.x, co = tid & 63, q = tid >> 6;
+  const int ntap = a.Cin * 49, HoWo = a.Ho * a.Wo, cog = blockIdx.y * 64;
+  float acc[40];
+#pragma unroll
+  for (int j = 0; j < 40; ++j) acc[j] = 0.f;
+  const long long pbeg = (long long)blockIdx.x * a.per;
+  const int pend = (int)min((long long)a.P, pbeg + a.per);
+  for (long long pl = pbeg; pl < pend; pl += kStemPx) {
+    const int p0 = (int)pl, pn = min(kStemPx, pend - p0);
+    for (int i = tid; i < kStemPx * kStemTaps; i += 256) {
+      const int px = i / kStemTaps, t = i - px * kStemTaps;
+      float v = 0.f;
+      if (px < pn && t < ntap) {
+        const int p = p0 + px, n = p / HoWo, rem = p - n * HoWo, oy = rem / a.Wo, ox = rem - oy * a.Wo;
+        const int ci = t / 49, r = t - ci * 49, ky = r / 7, kx = r - ky * 7;
+        const int jy = oy * 2 - 3 + ky, jx = ox * 2 - 3 + kx;
+        if (jy >= 0 && jy < a.Hi && jx >= 0 && jx < a.Wi) v = a.x[(((size_t)n * a.Cin + ci) * a.Hi + jy) * a.Wi + jx];
+      }
+      xs[px][t] = v;
+    }
+    for (int i = tid; i < kStemPx * 64; i += 256) {
+      const int px = i % kStemPx, c = i / kStemPx;
+      float v = 0.f;
+      if (px < pn) {
+        const int p = p0 + px, n = p / HoWo, rem = p - n * HoWo;
+        v = a.dy[((size_t)n * a.Cout + cog + c) * HoWo + rem];
+      }
+      dys[px][c] = v;
+    }
+    __syncthreads();
+    for (int px = 0; px < pn; ++px) {
+      const float g = dys[px][co];
+      const float4* __restrict__ xr = reinterpret_cast<const float4*>(&xs[px][q * 40]);
+#pragma unroll
+      for (int j = 0; j < 10; ++j) {
+        const float4 v = xr[j];
+        acc[4 * j] = fmaf(g, v.x, acc[4 * j]);
+        acc[4 * j + 1] = fmaf(g, v.y, acc[4 * j + 1]);
+        acc[4 * j + 2] = fmaf(g, v.z, acc[4 * j + 2]);
+        acc[4 * j + 3] = fmaf(g, v.w, acc[4 * j + 3]);
+      }
+    }
+    __syncthreads();
+  }
+  float* __restrict__ o = a.part + ((size_t)blockIdx.x * a.Cout + cog + co) * ntap;
+#pragma unroll
+  for (int j = 0; j < 40; ++j)
+    if (q * 40 + j < ntap) o[q * 40 + j] = acc[j];
+}
+__global__ __launch_bounds__(256) void stem7x7_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw, int S, int total) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  float s = 0.f;
+  for (int k = 0; k < S; ++k) s += part[(size_t)k * total + i];
+  dw[i] = s;
+}
+inline int stem7x7_split(long long P) { return (int)std::min<long long>(kStemMaxSplit, (P + kStemPx - 1) / kStemPx); }
 
 }  // namespace gc

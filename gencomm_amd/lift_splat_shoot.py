@@ -7,7 +7,14 @@
 Every operation of ``forward`` is a HIP kernel behind the C ABI: the trunk (7x7 stride-2 stem, max-pool, the bottlenecks of
 ``layer1`` / ``layer2`` with folded eval BatchNorm and the fused identity + ReLU) and the heads on ``conv2d_hip``; the depth softmax,
 geometry, sort and splat in ``gencomm_lss_splat_fwd`` (the ``depth (x) feature`` tensor is never formed); the depth targets of
-``depth_supervision`` in ``gencomm_lss_depth_target_fwd``. Inference only (the GenComm stage-2 model freezes the encoders).
+``depth_supervision`` in ``gencomm_lss_depth_target_fwd``.
+
+``LiftSplatShoot(args)`` is inference only (the GenComm stage-2 model freezes the encoders) and refuses a grad-enabled forward.
+``LiftSplatShoot(args, trainable=True)`` trains (stage 1 of the reference trains every encoder from scratch): the trunk and heads run
+through ``conv2d_hip``'s autograd paths (batch-statistics BatchNorm in ``.train()``; the 7x7 stem's weight gradient on
+``gencomm_stem7x7_wgrad``, the max-pool's on ``gencomm_maxpool3x3s2_bwd``), the lift-splat through ``_LiftSplatFn``
+(``gencomm_lss_splat_bwd``), and ``depth_items[0]`` stays attached to the graph for the depth term of the criteria. The images and the
+camera matrices get no gradient.
 """
 from __future__ import annotations
 
@@ -39,10 +46,30 @@ def depth_discretization(depth_min, depth_max, num_bins, mode):   # camera_utils
     raise NotImplementedError(f"grid_conf.mode {mode!r}: UD and LID are supported")
 
 
+class _MaxPoolFn(torch.autograd.Function):
+    """maxpool3x3s2 with its HIP backward (``gencomm_maxpool3x3s2_bwd``: every window's gradient goes to its arg-max, torch's tie rule)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        with torch.no_grad():
+            return maxpool3x3s2(x)
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        n, c, h, w = x.shape
+        dx = torch.empty_like(x)
+        _lib.check(_lib.lib().gencomm_maxpool3x3s2_bwd(ptr(x), ptr(f32c(gy)), ptr(dx), n, c, h, w, stream_ptr(x.device)), "gencomm_maxpool3x3s2_bwd")
+        return dx
+
+
 def maxpool3x3s2(x: torch.Tensor) -> torch.Tensor:
-    """nn.MaxPool2d(kernel_size=3, stride=2, padding=1) on the HIP kernel."""
+    """nn.MaxPool2d(kernel_size=3, stride=2, padding=1) on the HIP kernel (differentiable: HIP backward)."""
     require_gpu(x, "maxpool3x3s2")
     x = f32c(x)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _MaxPoolFn.apply(x)
     n, c, h, w = x.shape
     y = torch.empty(n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1, dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().gencomm_maxpool3x3s2_fwd(ptr(x), ptr(y), n, c, h, w, stream_ptr(x.device)), "gencomm_maxpool3x3s2_fwd")
@@ -127,14 +154,50 @@ class CamEncodeResnet101(nn.Module):
         return out
 
 
+class _LiftSplatFn(torch.autograd.Function):
+    """``LiftSplatShoot.splat`` with gradients for depth_logit and feat. The forward is the same three launches plus the sort, on a
+    workspace of its OWN (the per-device shared one would be overwritten by the next forward) that stays in the context together with
+    the cells; the backward is ``gencomm_lss_splat_bwd``. The camera matrices get None (the reference's ``.long()`` cuts that path)."""
+
+    @staticmethod
+    def forward(ctx, depth_logit, feat, module, rots, trans, intrins, post_rots, post_trans):
+        B, N = trans.shape[:2]
+        D, fH, fW = module.frustum.shape[:3]
+        Cc, dev = feat.shape[1], feat.device
+        nbytes = _lib.check_size(_lib.lib().gencomm_lss_workspace_bytes(B, N, D, fH, fW, Cc, module._grid()[2]), "gencomm_lss_workspace_bytes")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out, cell = module.splat(depth_logit, feat, rots, trans, intrins, post_rots, post_trans, return_cells=True, workspace=ws)
+        ctx.save_for_backward(ws, cell)
+        ctx.module, ctx.dims = module, (B, N, D, fH, fW, Cc)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ws, cell = ctx.saved_tensors
+        B, N, D, fH, fW, Cc = ctx.dims
+        dev = grad_out.device
+        l = _lib.lib()
+        nx = ctx.module._grid()[2]
+        nbytes = _lib.check_size(l.gencomm_lss_splat_bwd_workspace_bytes(B, Cc, nx), "gencomm_lss_splat_bwd_workspace_bytes")
+        scratch = workspaces.get(dev, nbytes, "lss_bwd")
+        g = f32c(grad_out)
+        d_logit = torch.empty(B * N, D, fH, fW, dtype=torch.float32, device=dev)
+        d_feat = torch.empty(B * N, Cc, fH, fW, dtype=torch.float32, device=dev)
+        _lib.check(l.gencomm_lss_splat_bwd(ptr(g), ptr(ws), ws.numel(), ptr(cell), nx, B, N, D, fH, fW, Cc, ptr(d_logit), ptr(d_feat),
+                                           ptr(scratch), scratch.numel(), stream_ptr(dev)), "gencomm_lss_splat_bwd")
+        return d_logit, d_feat, None, None, None, None, None, None
+
+
 class LiftSplatShoot(nn.Module):
     """heter_encoders.py:83-241 with ``camera_encoder: Resnet101``. ``forward(data_dict, modality_name)`` reads
     ``data_dict['inputs_<modality_name>']`` = {imgs [B, N, 4, H, W] (RGB + depth), rots, intrins, post_rots [B, N, 3, 3], trans,
     post_trans [B, N, 3]} and returns the BEV map [B, img_features * nz, ny, nx]; with ``depth_supervision`` it keeps
-    ``self.depth_items = (depth_logit [B N, D, fH, fW], depth_gt_indices [B N, fH, fW] int64)`` as the reference does."""
+    ``self.depth_items = (depth_logit [B N, D, fH, fW], depth_gt_indices [B N, fH, fW] int64)`` as the reference does.
+    ``trainable=True`` opts into the grad-enabled forward (HIP backward of every stage; ``depth_logit`` stays attached to the graph)."""
 
-    def __init__(self, args):
+    def __init__(self, args, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.grid_conf = args["grid_conf"]
         self.data_aug_conf = args["data_aug_conf"]
         self.camera_encoder_type = args["camera_encoder"]
@@ -173,9 +236,11 @@ class LiftSplatShoot(nn.Module):
         return ((C.c_float * 3)(*lo.tolist()), (C.c_float * 3)(*self.dx.numpy().astype(np.float32).tolist()),
                 (C.c_int * 3)(*[int(v) for v in self.nx.tolist()]))
 
-    def splat(self, depth_logit, feat, rots, trans, intrins, post_rots, post_trans, return_cells=False):
+    def splat(self, depth_logit, feat, rots, trans, intrins, post_rots, post_trans, return_cells=False, workspace=None):
         """get_geometry + voxel_pooling (+ QuickCumsum, griddify) on ``gencomm_lss_splat_fwd``: depth_logit [B N, D, fH, fW], feat
-        [B N, C, fH, fW] -> [B, C nz, ny, nx]; with ``return_cells`` also the reference's rank of every frustum point (-1 outside)."""
+        [B N, C, fH, fW] -> [B, C nz, ny, nx]; with ``return_cells`` also the reference's rank of every frustum point (-1 outside).
+        ``workspace``: a uint8 tensor of ``gencomm_lss_workspace_bytes`` the caller owns (``_LiftSplatFn``), else the shared one.
+        Not differentiable by itself: ``splat_grad`` is."""
         B, N = trans.shape[:2]
         D, fH, fW = self.frustum.shape[:3]
         Cc = feat.shape[1]
@@ -191,7 +256,7 @@ class LiftSplatShoot(nn.Module):
         nxs = [int(v) for v in self.nx.tolist()]
         l = _lib.lib()
         nbytes = _lib.check_size(l.gencomm_lss_workspace_bytes(B, N, D, fH, fW, Cc, nx), "gencomm_lss_workspace_bytes")
-        ws = workspaces.get(dev, nbytes, "lss")
+        ws = workspaces.get(dev, nbytes, "lss") if workspace is None else workspace
         out = torch.empty(B, Cc * nxs[2], nxs[1], nxs[0], dtype=torch.float32, device=dev)
         cell = torch.empty(B * N * D * fH * fW, dtype=torch.int32, device=dev) if return_cells else None
         dl, ft = f32c(depth_logit), f32c(feat)
@@ -199,10 +264,30 @@ class LiftSplatShoot(nn.Module):
                                            ptr(out), ptr(cell), ptr(ws), ws.numel(), stream_ptr(dev)), "gencomm_lss_splat_fwd")
         return (out, cell) if return_cells else out
 
+    def splat_grad(self, depth_logit, feat, rots, trans, intrins, post_rots, post_trans):
+        """``splat`` with gradients for depth_logit and feat (``_LiftSplatFn``)."""
+        require_gpu(feat, "LiftSplatShoot.splat_grad")
+        return _LiftSplatFn.apply(depth_logit, feat, self, rots, trans, intrins, post_rots, post_trans)
+
+    def _forward_train(self, x, rots, trans, intrins, post_rots, post_trans):
+        require_gpu(x, "LiftSplatShoot")
+        if x.requires_grad:
+            raise NotImplementedError("LiftSplatShoot(trainable=True): gradients with respect to imgs are not implemented -- the 7x7 stride-2 "
+                                      "stem (camencode.conv1) has a weight gradient only; pass imgs without requires_grad")
+        B, N, Cimg, imH, imW = x.shape
+        xf = f32c(x).view(B * N, Cimg, imH, imW)
+        depth_logit, feat = self.camencode(xf[:, :3].contiguous())
+        out = self.splat_grad(depth_logit, feat, rots, trans, intrins, post_rots, post_trans)
+        if self.depth_supervision:
+            self.depth_items = (depth_logit, self.camencode.depth_gt_indices(xf))   # depth_logit attached to the graph, as in the reference
+        return out
+
     def forward(self, data_dict, modality_name):
         inp = data_dict[f"inputs_{modality_name}"]
         x, rots, trans, intrins, post_rots, post_trans = (inp["imgs"], inp["rots"], inp["trans"], inp["intrins"], inp["post_rots"],
                                                           inp["post_trans"])
+        if self.trainable and torch.is_grad_enabled():
+            return self._forward_train(x, rots, trans, intrins, post_rots, post_trans)
         if torch.is_grad_enabled() and any(t.requires_grad for t in (x, rots, trans, intrins, post_rots, post_trans, *self.parameters())):
             raise NotImplementedError(
                 "LiftSplatShoot is inference only: gradients through the camera encoder are not implemented. The GenComm stage-2 model "

@@ -15,7 +15,9 @@ synchronises the host -- the reference calls ``.item()`` six times per step (``p
 ``point_pillar_gencomm_loss.py:50-55``), here ``loss_dict`` holds detached device scalars that ``logging`` converts when
 it prints.  One exception, inherited: an output dict that carries a DEVICE ``record_len`` makes ``int(record_len.sum())`` a
 device-to-host read, as in the reference (``point_pillar_loss.py:43-44``); a list or CPU tensor does not, and this package's
-shells emit neither.  Camera depth supervision (``depth_items*`` keys) and the IoU head are outside this build: their keys raise.
+shells emit neither.  Camera depth supervision (``depth_items*`` keys, ``point_pillar_depth_loss.py:37-57``) is the focal loss of the
+depth logits at the target bin: on float32 GPU tensors one launch per key (``gencomm_depth_focal_loss``: value and gradient), otherwise
+the composition ``depth_focal_loss`` below.  The IoU head is outside this build: its key raises.
 """
 from __future__ import annotations
 
@@ -86,7 +88,64 @@ class _HeadLossFn(torch.autograd.Function):
         return (flat[:n1].view(s1), flat[n1:n1 + n2].view(s2), flat[n1 + n2:].view(s3) if s3 is not None else None, None, None, None, None)
 
 
+def depth_focal_loss(depth_logit, depth_gt_indices, alpha=0.25, gamma=2.0):
+    """FocalLoss(alpha, gamma, reduction="none") of point_pillar_depth_loss.py:155-178, the reference's operator sequence:
+    depth_logit [N, D, H, W], depth_gt_indices int64 [N, H, W] -> per-pixel loss [N, H, W]."""
+    soft = depth_logit.softmax(1)
+    log_soft = depth_logit.log_softmax(1)
+    one_hot = F.one_hot(depth_gt_indices, num_classes=depth_logit.shape[1]).to(depth_logit).permute(0, 3, 1, 2)
+    focal = -alpha * torch.pow(-soft + 1.0, gamma) * log_soft
+    return torch.einsum("bc...,bc...->b...", (one_hot, focal))
+
+
+class _DepthFocalFn(torch.autograd.Function):
+    """``depth_focal_loss(...).mean() * weight`` and its gradient with respect to the logits in one launch (``gencomm_depth_focal_loss``,
+    float64 accumulation of the value); the backward is one multiply by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, logit, target, weight):
+        from . import _lib
+        from .runtime import ptr, stream_ptr, zeros as pool_zeros
+        n, D, H, W = logit.shape
+        grad = torch.empty_like(logit)
+        total = pool_zeros(1, torch.float64, logit.device)
+        _lib.check(_lib.lib().gencomm_depth_focal_loss(ptr(logit), ptr(target), ptr(grad), ptr(total), n, D, H, W, 0.25, 2.0,
+                                                       float(weight) / float(n * H * W), stream_ptr(logit.device)), "gencomm_depth_focal_loss")
+        ctx.save_for_backward(grad)
+        return total.float()[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+def depth_term(output_dict, suffix, depth_cfg, fuse=True):
+    """Sum over every ``depth_items{suffix}*`` key of FocalLoss(depth_logit, depth_gt_indices).mean() * depth.weight
+    (point_pillar_depth_loss.py:37-54); None when the dict carries no such key."""
+    keys = [k for k in output_dict if k.startswith(f"depth_items{suffix}")]
+    if not keys:
+        return None
+    if depth_cfg is None:
+        raise KeyError("loss.args.depth (weight) is needed for the depth_items of camera agents")
+    for key in ("smooth_target", "use_fg_mask"):
+        if depth_cfg.get(key):
+            raise NotImplementedError(f"loss.args.depth.{key} is outside this build (no shipped yaml sets it)")
+    weight = depth_cfg["weight"]
+    total = 0
+    for k in keys:
+        logit, target = output_dict[k][0], output_dict[k][1]
+        if (fuse and logit.is_cuda and logit.dtype == torch.float32 and logit.dim() == 4 and target.is_cuda and target.dtype == torch.int64
+                and tuple(target.shape) == (logit.shape[0],) + tuple(logit.shape[2:])):
+            total = total + _DepthFocalFn.apply(logit.contiguous(), target.contiguous(), weight)
+        else:
+            total = total + depth_focal_loss(logit, target).mean() * weight
+    return total
+
+
 class PointPillarGencommLoss(nn.Module):
+    with_generation = True      # PointPillarDepthLoss: the same head and depth terms without the generation term
+
     def __init__(self, args):
         super().__init__()
         if "iou" in args:
@@ -94,7 +153,7 @@ class PointPillarGencommLoss(nn.Module):
         self.pos_cls_weight = args["pos_cls_weight"]
         self.cls, self.reg, self.dir = args["cls"], args["reg"], args.get("dir")
         self.depth = args.get("depth")                      # parsed like the reference; only camera agents produce depth items
-        self.generate_weight = args["generate_weight"]
+        self.generate_weight = args["generate_weight"] if self.with_generation else None
         self.fuse_heads = True      # False: always the composition of framework operators (tests compare the two)
         self.loss_dict = {}
 
@@ -138,8 +197,19 @@ class PointPillarGencommLoss(nn.Module):
         return _HeadLossFn.apply(c(cls), c(reg), c(dirp) if dirp is not None else None, c(pos), c(neg), c(tgt), cfg)
 
     def forward(self, output_dict, target_dict, suffix=""):
-        if any(k.startswith(f"depth_items{suffix}") for k in output_dict):
-            raise NotImplementedError("depth supervision of camera agents is outside this build")
+        total = self._head_terms(output_dict, target_dict, suffix)          # loss_dict: reg / cls / dir and their sum as total_loss
+        depth = depth_term(output_dict, suffix, self.depth, self.fuse_heads)
+        if depth is not None:                                               # point_pillar_depth_loss.py:56-57: added to the returned loss;
+            total = total + depth                                           # the logged total_loss is not updated by this term itself
+            self.loss_dict["depth_loss"] = depth.detach()
+        if not self.with_generation:
+            return total
+        gen_loss = F.mse_loss(output_dict["gt_feature"], output_dict["pred_feature"])   # point_pillar_gencomm_loss.py:46-55
+        total = total + self.generate_weight * gen_loss
+        self.loss_dict.update({"generate_loss": gen_loss.detach(), "total_loss": total.detach()})
+        return total
+
+    def _head_terms(self, output_dict, target_dict, suffix):
         if "record_len" in output_dict:
             # point_pillar_loss.py:43-44.  A list / CPU tensor costs nothing; a DEVICE tensor makes this line a device-to-host read,
             # exactly as in the reference -- the shells of this package do not put `record_len` into their output dict, so the
@@ -159,9 +229,7 @@ class PointPillarGencommLoss(nn.Module):
             self.loss_dict = {"reg_loss": parts[1], "cls_loss": parts[0]}
             if self.dir:
                 self.loss_dict["dir_loss"] = parts[2]
-            gen_loss = F.mse_loss(output_dict["gt_feature"], output_dict["pred_feature"])
-            total = total + self.generate_weight * gen_loss
-            self.loss_dict.update({"generate_loss": gen_loss.detach(), "total_loss": total.detach()})
+            self.loss_dict["total_loss"] = total.detach()
             return total
         cls_labels = target_dict["pos_equal_one"].view(bs, -1, 1)
         positives = cls_labels > 0
@@ -186,17 +254,19 @@ class PointPillarGencommLoss(nn.Module):
             dir_loss = (F.cross_entropy(logits, tgt.view(-1), reduction="none") * reg_w.flatten()).sum() * self.dir["weight"] / bs
             total = total + dir_loss
             self.loss_dict["dir_loss"] = dir_loss.detach()
-        gen_loss = F.mse_loss(output_dict["gt_feature"], output_dict["pred_feature"])   # point_pillar_gencomm_loss.py:46-52
-        total = total + self.generate_weight * gen_loss
-        self.loss_dict.update({"generate_loss": gen_loss.detach(), "total_loss": total.detach()})
+        self.loss_dict["total_loss"] = total.detach()
         return total
 
     def logging(self, epoch, batch_id, batch_len, writer=None, suffix="", iter=None):  # point_pillar_gencomm_loss.py:61-104 (no wandb)
         d = {k: float(v) for k, v in self.loss_dict.items()}   # the only host synchronisation of the criterion
-        print("[epoch %d][%d/%d]%s || Loss: %.4f || Conf Loss: %.4f || Loc Loss: %.4f || Dir Loss: %.4f || Gen Loss: %.4f" % (
+        line = "[epoch %d][%d/%d]%s || Loss: %.4f || Conf Loss: %.4f || Loc Loss: %.4f || Dir Loss: %.4f || Gen Loss: %.4f" % (
             epoch, batch_id + 1, batch_len, suffix, d.get("total_loss", 0), d.get("cls_loss", 0), d.get("reg_loss", 0),
-            d.get("dir_loss", 0), d.get("generate_loss", 0)))
+            d.get("dir_loss", 0), d.get("generate_loss", 0))
+        if "depth_loss" in d:
+            line += " || Depth Loss: %.4f" % d["depth_loss"]
+        print(line)
         if writer is not None:
-            for tag, key in (("Regression_loss", "reg_loss"), ("Confidence_loss", "cls_loss"), ("Dir_loss", "dir_loss"), ("Gen_loss", "generate_loss")):
+            tags = (("Regression_loss", "reg_loss"), ("Confidence_loss", "cls_loss"), ("Dir_loss", "dir_loss"), ("Gen_loss", "generate_loss"))
+            for tag, key in tags + ((("Depth_loss", "depth_loss"),) if "depth_loss" in d else ()):
                 writer.add_scalar(tag + suffix, d.get(key, 0), epoch * batch_len + batch_id)
         return d

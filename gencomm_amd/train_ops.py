@@ -90,6 +90,19 @@ def conv2d_wgrad(dy: torch.Tensor, x: torch.Tensor, k: int, pad: int, bias: bool
     return dw, db
 
 
+def stem7x7_wgrad(dy: torch.Tensor, x: torch.Tensor, cout: int) -> torch.Tensor:
+    """Weight gradient [cout, cin, 7, 7] of a 7x7 stride-2 pad-3 convolution (cin <= 3, cout a multiple of 64: the ResNet stem) from
+    dy [n, cout, Ho, Wo] and x [n, cin, H, W]: partial sums over pixel ranges, added in a fixed order (no atomics)."""
+    dy, x = _c(dy), _c(x)
+    n, cin, H, W = x.shape
+    l = _lib.lib()
+    need = _lib.check_size(l.gencomm_stem7x7_wgrad_scratch_floats(n, cin, H, W, cout), "gencomm_stem7x7_wgrad_scratch_floats")
+    scratch = torch.empty(need, dtype=torch.float32, device=x.device)
+    dw = torch.empty(cout, cin, 7, 7, dtype=torch.float32, device=x.device)
+    _lib.check(l.gencomm_stem7x7_wgrad(ptr(dy), ptr(x), ptr(dw), n, cin, H, W, cout, ptr(scratch), need, stream_ptr(x.device)), "gencomm_stem7x7_wgrad")
+    return dw
+
+
 def conv2d_dgrad_strided(dy: torch.Tensor, w: torch.Tensor, pad: int, stride: int, in_hw: Tuple[int, int]) -> torch.Tensor:
     """Input gradient of a stride-s convolution: dy is spread onto the stride-1 output grid (zeros in between: a strided copy),
     then the stride-1 input-gradient convolution runs on the HIP kernel. `in_hw` = (H, W) of the forward input."""

@@ -739,6 +739,36 @@ int gencomm_lss_depth_target_fwd(const float* imgs, int BN, int Cimg, int H, int
                                  int num_bins, long long* indices, unsigned char* mask, void* stream);
 int gencomm_maxpool3x3s2_fwd(const float* x, float* y, int N, int C, int H, int W, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Training the camera encoder (added within ABI v12).
+ *   gencomm_lss_splat_bwd   gradients of gencomm_lss_splat_fwd with respect to depth_logit and feat from grad_out [B][nz C][ny][nx]:
+ *                           fwd_workspace = the workspace of the forward call being differentiated (its softmax probabilities
+ *                           and pixel-major feature rows are read from it: the caller keeps it untouched until the backward), cell =
+ *                           that call's `cell` output -> d_depth_logit [B N][D][fH][fW], d_feat [B N][C][fH][fW] (every element
+ *                           written). The camera matrices get no gradient (the reference's .long() cuts that path). D <= 256.
+ *                           Scratch: gencomm_lss_splat_bwd_workspace_bytes (the cell-major copy of grad_out). Two launches, no sort,
+ *                           no atomics, no memset, no host synchronisation: two runs are bit-identical.
+ *   gencomm_maxpool3x3s2_bwd  dx [N][C][H][W] of gencomm_maxpool3x3s2_fwd from x and dy [N][C][Ho][Wo]: every window's dy goes to its
+ *                           arg-max (first element in row-major window order with v > m || isnan(v), torch's tie rule); gather, no atomics
+ *   gencomm_stem7x7_wgrad   weight gradient dw [Cout][Cin][7][7] of a 7x7 stride-2 pad-3 convolution (Cin <= 3, Cout a multiple of
+ *                           64: the ResNet stem) from dy [N][Cout][Ho][Wo] and x [N][Cin][Hi][Wi]; scratch >=
+ *                           gencomm_stem7x7_wgrad_scratch_floats floats (partial sums over pixel ranges, added in a fixed order)
+ *   gencomm_depth_focal_loss  depth term of PointPillarDepthLoss (FocalLoss, point_pillar_depth_loss.py:105-185, no smoothing, no
+ *                           foreground mask): *sum += scale * sum over pixels of -alpha (1 - p_t)^gamma log p_t (float64; the caller
+ *                           zeroes it) and grad [BN][D][H][W] = d (that value) / d depth_logit, from depth_logit [BN][D][H][W] and
+ *                           target int64 [BN][H][W]; scale = weight / (BN H W). One launch.
+ * -------------------------------------------------------------------------------------------- */
+long long gencomm_lss_splat_bwd_workspace_bytes(int B, int C, const int* nx3);
+int gencomm_lss_splat_bwd(const float* grad_out, const void* fwd_workspace, long long fwd_workspace_bytes, const int* cell, const int* nx3,
+                          int B, int N, int D, int fH, int fW, int C, float* d_depth_logit, float* d_feat, void* workspace,
+                          long long workspace_bytes, void* stream);
+int gencomm_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx, int N, int C, int H, int W, void* stream);
+long long gencomm_stem7x7_wgrad_scratch_floats(int N, int Cin, int Hi, int Wi, int Cout);
+int gencomm_stem7x7_wgrad(const float* dy, const float* x, float* dw, int N, int Cin, int Hi, int Wi, int Cout, float* scratch,
+                          long long scratch_floats, void* stream);
+int gencomm_depth_focal_loss(const float* depth_logit, const long long* target, float* grad, double* sum, int BN, int D, int H, int W,
+                             float alpha, float gamma, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
