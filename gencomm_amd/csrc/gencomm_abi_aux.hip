@@ -1,6 +1,6 @@
 // Second translation unit of libgencomm_hip.so: iou3d_nms (reference extension semantics), the point-cloud voxeliser,
 // the V2X-ViT attention kernels, the sparse 3-D convolutions of the SECOND encoder, the Lift-Splat-Shoot camera encoder
-// and the training-time anchor target assignment.
+// the training-time anchor target assignment and the batched lidar front end.
 // Kept apart from gencomm_abi.hip so that the rocPRIM templates do not lengthen the hot path's compile.
 #include "../../include/gencomm_hip.h"
 
@@ -13,6 +13,7 @@
 #include "sparse_kernels.h"
 #include "target_kernels.h"
 #include "v2xvit_kernels.h"
+#include "voxel_batch_kernels.h"
 #include "voxel_kernels.h"
 
 using namespace gc;
@@ -83,6 +84,42 @@ int gencomm_voxelize_fwd(const float* points, int n, int nfeat, const float* vox
   GC_CHECK_ARG(voxels && coords_zyx && num_points && count && workspace && (n == 0 || points), "null pointer");
   if ((long long)voxel_ws(n).total > workspace_bytes) return fail(GC_ERR_WORKSPACE, "workspace too small (gencomm_voxelize_workspace_bytes)");
   return voxelize_enqueue(a, voxels, coords_zyx, num_points, count, (char*)workspace, (hipStream_t)stream);
+}
+
+long long gencomm_voxelize_batch_workspace_bytes(int n, int A, int max_voxels) {
+  if (n < 0 || A < 1 || max_voxels < 1) { fail(GC_ERR_ARG, "n must be non-negative, A and max_voxels positive"); return -1; }
+  return (long long)voxel_batch_ws(n, A, (int)std::min<long long>((long long)A * max_voxels, n)).total;
+}
+
+int gencomm_voxelize_batch_fwd(const float* points, int n, int nfeat, const int* offsets, int A, const float* transforms, const int* perm, int mask_ego,
+                               const float* voxel_size3, const float* range6, int max_points, int max_voxels, int cap_rows, float* voxels,
+                               int* coords_azyx, int* num_points, int* counts, int* total, void* workspace, long long workspace_bytes, void* stream) {
+  GC_CHECK_ARG(n >= 0 && A >= 1 && nfeat >= 3 && max_points >= 1 && max_voxels >= 1 && voxel_size3 && range6, "bad n / A / nfeat / max_points / max_voxels");
+  VoxelBatchArgs a{};
+  a.points = points; a.offsets = offsets; a.tfm = transforms; a.perm = perm;
+  a.n = n; a.nfeat = nfeat; a.A = A; a.mask_ego = mask_ego ? 1 : 0; a.max_points = max_points; a.max_voxels = max_voxels;
+  double cells = 1.0;
+  a.ncells = 1;
+  for (int j = 0; j < 3; ++j) {
+    a.vs[j] = voxel_size3[j]; a.r0[j] = range6[j];
+    GC_CHECK_ARG(voxel_size3[j] > 0.f, "voxel size must be positive");
+    const float g = rintf((range6[3 + j] - range6[j]) / voxel_size3[j]);   // as gencomm_voxelize_fwd: np.round((range[3:6] - range[0:3]) / voxel_size)
+    GC_CHECK_ARG(g >= 1.f, "empty grid");
+    GC_CHECK_ARG(g < 2147483648.f, "more than 2^31 - 1 cells along one axis");
+    a.grid[j] = (int)g;
+    cells *= (double)a.grid[j];
+  }
+  GC_CHECK_ARG((double)A * cells < 9.2e18, "A * cells does not fit the 64-bit keys (limit 2^63)");
+  a.ncells = (unsigned long long)a.grid[0] * a.grid[1] * a.grid[2];
+  const long long cap = std::min<long long>((long long)A * max_voxels, n);
+  GC_CHECK_ARG(cap_rows == cap, "cap_rows must be min(A * max_voxels, n)");
+  a.cap_rows = cap_rows;
+  GC_CHECK_ARG(offsets && counts && total && workspace, "null pointer");
+  GC_CHECK_ARG(n == 0 || (points && voxels && coords_azyx && num_points), "null pointer");
+  GC_CHECK_ARG(((uintptr_t)coords_azyx & 15) == 0, "coords must be 16-byte aligned");
+  if ((long long)voxel_batch_ws(n, A, cap_rows).total > workspace_bytes) return fail(GC_ERR_WORKSPACE, "workspace too small (gencomm_voxelize_batch_workspace_bytes)");
+  const bool vec4 = nfeat == 4 && (((uintptr_t)points | (uintptr_t)voxels) & 15) == 0;
+  return voxelize_batch_enqueue(a, vec4, voxels, coords_azyx, num_points, counts, total, (char*)workspace, (hipStream_t)stream);
 }
 
 int gencomm_warp_affine_fwd(const float* x, const double* theta, float* out, int n, int C, int H, int W, void* stream) {

@@ -513,6 +513,28 @@ int gencomm_voxelize_fwd(const float* points, int n, int nfeat, const float* vox
                          void* workspace, long long workspace_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Batched lidar front end: the raw clouds of all A agents of a call -> collated voxels in one launch sequence, with no host
+ * read and no per-call memset (csrc/voxel_batch_kernels.h). Per agent: shuffle (perm, an INPUT), mask_ego_points
+ * (pcd_utils.py:84-86: the closed box -1.95 <= x <= 2.95, -1.1 <= y <= 1.1 is removed, before the projection),
+ * project_points_by_matrix_torch (box_utils.py:1169: float32 fused multiply-add chain over (x, y, z, 1); x, y, z only are
+ * replaced), then exactly the gencomm_voxelize_fwd result of that agent's points (max_points and max_voxels per agent), then
+ * SpVoxelPreprocessor.collate_batch: agents back to back, the agent index in front of (z, y, x).
+ *   points [n][nfeat] float32; offsets [A + 1] device int32, logical point i belongs to agent a when offsets[a] <= i <
+ *   offsets[a + 1]; transforms [A][16] float32 row-major 4x4 or null; perm [n] device int32 or null: logical point i is input
+ *   row perm[i] (a row index outside [0, n) drops the point); mask_ego 0 / 1.
+ *   cap_rows = min(A * max_voxels, n) rows are the capacity of voxels [cap_rows][max_points][nfeat], coords_azyx [cap_rows][4]
+ *   (16-byte aligned) and num_points [cap_rows]; counts [A] and *total (device ints) = voxels per agent and their sum. Rows
+ *   [0, total) are written completely (zero padding included), the rows behind them are not touched.
+ * Keys are agent * cells + cell: 32 bits where A * cells < 2^32, 64 bits otherwise; an argument error (status 1) when A * cells reaches 2^63.
+ * Deterministic: one stable radix sort, scans, one writer per output element, no atomics.
+ * -------------------------------------------------------------------------------------------- */
+long long gencomm_voxelize_batch_workspace_bytes(int n, int A, int max_voxels);
+int gencomm_voxelize_batch_fwd(const float* points, int n, int nfeat, const int* offsets, int A, const float* transforms, const int* perm,
+                               int mask_ego, const float* voxel_size3, const float* range6, int max_points, int max_voxels, int cap_rows,
+                               float* voxels, int* coords_azyx, int* num_points, int* counts, int* total,
+                               void* workspace, long long workspace_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * V2X-ViT fusion building blocks (opencood/models/fuse_modules/fusion_in_one.py:355-407, sub_modules/hmsa.py:117-150,
  * sub_modules/mswin.py:47-83); NCHW fp32 per agent. The Linear layers around them run through gencomm_conv2d_fwd (1x1),
  * the LayerNorms through gencomm_ln_nchw_fwd; gencomm_amd/v2xvit.py is the module with the reference's state_dict keys.
