@@ -6,6 +6,7 @@ Public surface mirrors the reference's plugin API:
     DiffusionUNet(config)              opencood/models/gencomm_modules/unet.py:198
     Enhancer(C, win_size, num_heads)   opencood/models/gencomm_modules/enhancer.py:359
     AttFusion(feature_dims)            opencood/models/fuse_modules/fusion_in_one.py:126
+    CoBEVT(args)                       opencood/models/fuse_modules/fusion_in_one.py:409 (fusion_method: cobevt; inference)
     regroup, normalize_pairwise_tfm    fusion_in_one.py:48, opencood/utils/transformation_utils.py:68
     MessageExtractorv2(in_ch, out_ch)  opencood/models/gencomm_modules/message_extractor_v2.py:109
     LiftSplatShoot(args)               opencood/models/heter_encoders.py:83 (camera_encoder: Resnet101; trainable=True trains it)
@@ -13,6 +14,7 @@ Public surface mirrors the reference's plugin API:
 
 All compute runs in hand-written HIP kernels behind the C ABI of ``include/gencomm_hip.h``.
 """
+from .cobevt import CoBEVT
 from .cond_diff import GenComm
 from .enhancer import Enhancer
 from .fusion import AttFusion, normalize_pairwise_tfm, regroup
@@ -34,5 +36,5 @@ def set_denoise_dtype(dtype) -> None:
     _lib.check(_lib.lib().gencomm_set_mode(_lib.MODE_ARITH, value), "gencomm_set_mode")
 
 
-__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "regroup", "normalize_pairwise_tfm",
+__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "CoBEVT", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "regroup", "normalize_pairwise_tfm",
            "set_denoise_dtype"]

@@ -1,6 +1,6 @@
 // Second translation unit of libgencomm_hip.so: iou3d_nms (reference extension semantics), the point-cloud voxeliser,
 // the V2X-ViT attention kernels, the sparse 3-D convolutions of the SECOND encoder, the Lift-Splat-Shoot camera encoder
-// the training-time anchor target assignment and the batched lidar front end.
+// the training-time anchor target assignment, the batched lidar front end and CoBEVT's swap attention.
 // Kept apart from gencomm_abi.hip so that the rocPRIM templates do not lengthen the hot path's compile.
 #include "../../include/gencomm_hip.h"
 
@@ -11,6 +11,7 @@
 #include "loss_kernels.h"
 #include "lss_kernels.h"
 #include "sparse_kernels.h"
+#include "swap_attn_kernels.h"
 #include "target_kernels.h"
 #include "v2xvit_kernels.h"
 #include "voxel_batch_kernels.h"
@@ -168,6 +169,35 @@ int gencomm_win_attn_fwd(const float* qkv, const float* pos_embedding, float* ou
   if (window == 8 && dim_head == 64) return win_attn_launch<64, 8>(a, n, st);
   if (window == 16 && dim_head == 32) return win_attn_launch<32, 16>(a, n, st);
   return fail(GC_ERR_ARG, "window attention: supported (window, dim_head) pairs are (4,16) (4,32) (8,16) (8,32) (8,64) (16,32) (16,64)");
+}
+
+// ---- CoBEVT (swap_attn_kernels.h) ---------------------------------------------------------------------------------------
+int gencomm_swap_attn_fwd(const float* qkv, const float* bias_table, const int* num_agents, float* out, int B, int L, int heads, int dim_head,
+                          int window, int H, int W, int grid_mode, void* stream) {
+  GC_CHECK_ARG(qkv && bias_table && num_agents && out, "null pointer");
+  GC_CHECK_ARG(B >= 1 && B <= 65535 && heads >= 1 && heads <= 65535, "swap attention: 1..65535 scenes and heads");
+  GC_CHECK_ARG(L >= 1 && L <= kSwapMaxAgents, "swap attention: agent_size (L) must be 1..8");
+  GC_CHECK_ARG(grid_mode == 0 || grid_mode == 1, "swap attention: grid_mode must be 0 (window partition) or 1 (grid partition)");
+  GC_CHECK_ARG(window == 4 || window == 8, "swap attention: window_size must be 4 or 8");
+  GC_CHECK_ARG(dim_head == 16 || dim_head == 32 || dim_head == 64, "swap attention: dim_head must be 16, 32 or 64");
+  GC_CHECK_ARG(H >= window && W >= window && H % window == 0 && W % window == 0, "swap attention: H and W must be multiples of window_size");
+  GC_CHECK_ARG((long long)H * W * 3 * heads * dim_head < (1LL << 31), "swap attention: one agent's qkv map must stay below 2^31 elements");
+  SwapArgs a{qkv, bias_table, num_agents, out, L, heads, H, W, grid_mode, 0, 0, 1.0f / sqrtf((float)dim_head)};
+  hipStream_t st = (hipStream_t)stream;
+  if (window == 4 && dim_head == 16) return swap_attn_launch<16, 4>(a, B, st);
+  if (window == 4 && dim_head == 32) return swap_attn_launch<32, 4>(a, B, st);
+  if (window == 4 && dim_head == 64) return swap_attn_launch<64, 4>(a, B, st);
+  if (window == 8 && dim_head == 16) return swap_attn_launch<16, 8>(a, B, st);
+  if (window == 8 && dim_head == 32) return swap_attn_launch<32, 8>(a, B, st);
+  return swap_attn_launch<64, 8>(a, B, st);
+}
+
+int gencomm_agent_mean_fwd(const float* x, float* out, int B, int L, long long count, void* stream) {
+  GC_CHECK_ARG(x && out, "null pointer");
+  GC_CHECK_ARG(B >= 1 && B <= 65535 && L >= 1 && count >= 1 && (count + 255) / 256 < (1LL << 31), "agent mean: bad B / L / count");
+  agent_mean_kernel<<<dim3((unsigned)((count + 255) / 256), B), 256, 0, (hipStream_t)stream>>>(x, out, L, count);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
 }
 
 // ---- V2X-ViT backward building blocks (v2xvit_kernels.h) ----------------------------------------------------------------

@@ -1,0 +1,198 @@
+// CoBEVT fusion (reference: opencood/models/fuse_modules/fusion_in_one.py:409-464 + fuse_modules/swap_fusion_modules.py) -- the
+// attention core of SwapFusionBlockMask's `Attention` (swap_fusion_modules.py:87-128).  Everything around it runs on kernels the
+// library already has (warp_affine_kernel, the LayerNorm and the 1x1 implicit-GEMM convolution for every Linear).
+//   swap_attn_kernel   per scene, head and GROUP (one ws x ws window or one grid cell of the map): attention over the group's
+//                      L * ws * ws tokens (agent l, w1, w2) JOINTLY, softmax(q k^T dim_head^-0.5 + bias[rel(i, j)], keys of agents
+//                      l >= N_b masked) v, with the 3-D relative position bias
+//                        rel = (li - lj + L - 1)(2 ws - 1)^2 + (hi - hj + ws - 1)(2 ws - 1) + (wi - wj + ws - 1)
+//                      (= the module's relative_position_index buffer, :63-85) computed in the kernel.
+//   agent_mean_kernel  the head's mean over the L agent rows of a scene (mlp_head's Reduce, :275).
+// Partitions are index arithmetic on the NCHW maps, nothing is rearranged in memory (X = H / ws, Y = W / ws):
+//   window  token (l, w1, w2) of group (x, y) = pixel (x ws + w1, y ws + w2) of agent l       '(x w1) (y w2)', :173-176
+//   grid    token (l, w1, w2) of group (x, y) = pixel (w1 X + x, w2 Y + y) of agent l         '(w1 x) (w2 y)', :184-187
+// QUERIES of padded agents (l >= N_b) are computed like any other: their rows are zero only before the first residual and enter the
+// final mean over all L agents; only their KEYS are masked.  The ego (agent 0) is always valid, so no row is fully masked.
+//
+// fp32 in, out and accumulation on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 products, an fmaf chain), in the
+// arrangement of win_attn_mfma_kernel: a wave owns one block of 32 queries and walks the keys in blocks of 32,
+//   S^T[key][query] = K Q^T   A = K rows from LDS, B = Q (scaled) from registers; a lane then owns ONE query column and 16 of the 32
+//                             keys (the others in lane ^ 32): softmax statistics are register-local plus one exchange;
+//   O^T[d][query] += V^T P    A = V rows from LDS in the key order the P registers already have, B = P from the registers.
+// 320 tokens (L 5, ws 8) x dim_head 64 of K and V are 166 KB: the keys are staged in tiles of 64 ([key][DH + 1] rows: odd stride,
+// conflict-free fills and operand reads) with a running softmax.  64 keys are four agents of a 4 x 4 group or one agent of an 8 x 8
+// group, so the key loop ends at the last VALID agent: masked agents cost nothing at ws 8 and at most part of one tile at ws 4.
+// A workgroup = up to 8 query blocks of one (group, head, scene); a group of more than 256 tokens is split evenly over several
+// workgroups, each staging the group's keys for itself.
+#pragma once
+#include "common.h"
+
+namespace gc {
+
+constexpr int kSwapMaxAgents = 8;  // MAX_AGENTS_PER_SCENE of the Python package
+
+struct SwapArgs {
+  const float* qkv;     // [B * L][3 * inner][H][W] (q | k | v blocks of inner = heads * DH channels, head-major)
+  const float* table;   // relative_position_bias_table [(2 L - 1)(2 WS - 1)^2][heads]
+  const int* nvalid;    // [B] agents present in each scene (clamped to 1 .. L here: the host never reads it)
+  float* out;           // [B * L][inner][H][W]
+  int L, heads, H, W, grid_mode;
+  int nqb, wpc;         // query blocks of 32 per group; query blocks (= waves) per workgroup
+  float scale;
+};
+
+using f32x16s = __attribute__((ext_vector_type(16))) float;
+
+template <int DH, int WS>
+__global__ __launch_bounds__(512) void swap_attn_kernel(const SwapArgs a) {
+  constexpr int T1 = WS * WS, KT = 64, LDK = DH + 1, DV = DH < 32 ? 32 : DH, LDV = DV + 1, PW = 2 * WS - 1, PW2 = PW * PW;
+  constexpr int CH = DH < 32 ? DH : 32;   // channels a fill thread has in flight
+  static_assert(KT % T1 == 0 && DH % 16 == 0 && DH <= 64, "4 x 4 or 8 x 8 groups, head width 16, 32 or 64");
+  extern __shared__ float sw_smem[];  // K [KT][LDK], V [KT][LDV] (columns DH .. 31 zero when DH < 32), bias of this head [(2 L - 1) PW2]
+  float* sK = sw_smem;
+  float* sV = sK + KT * LDK;
+  float* sP = sV + KT * LDV;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int nchunk = (a.nqb + a.wpc - 1) / a.wpc;
+  const int grp = blockIdx.x / nchunk, chunk = blockIdx.x - grp * nchunk;
+  const int m = blockIdx.y, b = blockIdx.z;
+  const int X = a.H / WS, Y = a.W / WS, L = a.L;
+  const int gx = grp / Y, gy = grp - gx * Y;
+  const int T = L * T1;                                   // tokens = queries of the group
+  const int TV = min(max(a.nvalid[b], 1), L) * T1;        // its valid keys: the agents present come first
+  const int inner = a.heads * DH, HW = a.H * a.W;
+  const size_t agent = (size_t)3 * inner * HW;
+  const float* __restrict__ base = a.qkv + (size_t)b * L * agent;
+  // pixel of the token's (w1, w2) inside this group
+  auto pixel = [&](int w1, int w2) { return a.grid_mode ? (w1 * X + gx) * a.W + w2 * Y + gy : (gx * WS + w1) * a.W + gy * WS + w2; };
+
+  for (int i = tid; i < (2 * L - 1) * PW2; i += nthr) sP[i] = a.table[(size_t)i * a.heads + m];
+  if (DV != DH)
+    for (int i = tid; i < KT * LDV; i += nthr) sV[i] = 0.f;   // the columns beyond DH are never written again
+
+  // wave = one block of 32 queries (lanes l and l + 32 share a query)
+  const int wave = tid >> 6, lane = tid & 63, qi = lane & 31, h = lane >> 5;
+  const int qb = chunk * a.wpc + wave;
+  const bool wave_live = wave < a.wpc && qb < a.nqb;      // wave-uniform; a wave without queries still fills and meets the barriers
+  const int qtok = qb * 32 + qi;
+  const bool qok = wave_live && qtok < T;
+  const int qt = qok ? qtok : 0;
+  const int ql = qt / T1, qh = (qt % T1) / WS, qw = qt % WS;
+  const int qpix = pixel(qh, qw);
+  float qv[DH / 2];
+#pragma unroll
+  for (int s = 0; s < DH / 2; ++s) qv[s] = qok ? base[ql * agent + (size_t)(m * DH + 2 * s + h) * HW + qpix] * a.scale : 0.f;
+  f32x16s o[DV / 32];
+#pragma unroll
+  for (int db = 0; db < DV / 32; ++db)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[db][i] = 0.f;
+  float mrun = -INFINITY, den = 0.f;
+  const int pbase = (ql + L - 1) * PW2 + (qh + WS - 1) * PW + (qw + WS - 1);
+
+  for (int k0 = 0; k0 < TV; k0 += KT) {
+    __syncthreads();   // the previous tile is no longer read (first pass: the bias and the zero fill are complete after the next one)
+    for (int e = tid; e < 2 * KT; e += nthr) {   // one (key, K or V) row per pass; keys beyond the valid ones become zero rows
+      const int row = e & (KT - 1), isv = e / KT, key = k0 + row;
+      const bool live = key < TV;
+      const int kt = live ? key : 0;
+      const int kl = kt / T1, pix = pixel((kt % T1) / WS, kt % WS);
+      const float* __restrict__ src = base + kl * agent + (size_t)((1 + isv) * inner + m * DH) * HW + pix;
+      float* __restrict__ dst = isv ? sV + row * LDV : sK + row * LDK;
+#pragma unroll
+      for (int c0 = 0; c0 < DH; c0 += CH) {
+        float v[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) v[c] = live ? src[(size_t)(c0 + c) * HW] : 0.f;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) dst[c0 + c] = v[c];
+      }
+    }
+    __syncthreads();
+    if (!wave_live) continue;
+    const int nkb = (min(KT, TV - k0) + 31) >> 5;   // every walked block of 32 begins with a valid key
+#pragma unroll 1
+    for (int kb = 0; kb < nkb; ++kb) {
+      f32x16s sc;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) sc[i] = 0.f;
+      const float* __restrict__ kr = sK + (32 * kb + qi) * LDK + h;
+#pragma unroll
+      for (int s = 0; s < DH / 2; ++s) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[2 * s], qv[s], sc, 0, 0, 0);
+      float bm = -INFINITY;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = k0 + 32 * kb + 8 * (r >> 2) + 4 * h + (r & 3);
+        const bool kok = key < TV;
+        const int koff = (key / T1) * PW2 + ((key % T1) / WS) * PW + key % WS;   // rel(query, key) = pbase - koff
+        const float bias = sP[kok ? pbase - koff : 0];
+        sc[r] = kok ? sc[r] + bias : -INFINITY;
+        bm = fmaxf(bm, sc[r]);
+      }
+      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));   // finite: the block's first key is valid
+      const float nm = fmaxf(mrun, bm), corr = expf(mrun - nm);
+      float ps = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { sc[r] = expf(sc[r] - nm); ps += sc[r]; }
+      den = den * corr + ps;
+      mrun = nm;
+#pragma unroll
+      for (int db = 0; db < DV / 32; ++db)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[db][i] *= corr;
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        const int keyl = 32 * kb + 8 * (t >> 2) + 4 * h + (t & 3);
+#pragma unroll
+        for (int db = 0; db < DV / 32; ++db)  // the head's 32-wide halves alternate: consecutive MFMAs never share an accumulator
+          o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(sV[keyl * LDV + 32 * db + qi], sc[t], o[db], 0, 0, 0);
+      }
+    }
+  }
+  if (!qok) return;   // no barrier follows
+  den += __shfl_xor(den, 32, 64);   // the partner lane holds the same query: it is live too
+  const float rden = 1.0f / den;
+  float* __restrict__ op = a.out + ((size_t)(b * L + ql) * inner + m * DH) * HW + qpix;
+#pragma unroll
+  for (int db = 0; db < DV / 32; ++db)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int ch = 32 * db + 8 * (r >> 2) + 4 * h + (r & 3);
+      if (DH >= 32 || (r >> 2) < DH / 8) op[(size_t)ch * HW] = o[db][r] * rden;
+    }
+}
+
+inline void swap_attn_klog(int dh, int ws) {
+  if (!klog_armed()) return;
+  char name[64];
+  snprintf(name, sizeof name, "swap_attn_kernel<%d,%d>", dh, ws);
+  klog_note(name);
+}
+
+template <int DH, int WS>
+inline int swap_attn_launch(SwapArgs a, int B, hipStream_t st) {
+  constexpr int DV = DH < 32 ? 32 : DH, PW = 2 * WS - 1;
+  a.nqb = (a.L * WS * WS + 31) / 32;
+  const int split = (a.nqb + 7) / 8;            // workgroups per group: at most 8 query blocks each, evenly
+  a.wpc = (a.nqb + split - 1) / split;
+  const int nchunk = (a.nqb + a.wpc - 1) / a.wpc;
+  const size_t shm = ((size_t)64 * (DH + 1) + 64 * (DV + 1) + (2 * a.L - 1) * PW * PW) * sizeof(float);
+  if (shm > 48 * 1024) GC_HIP(hipFuncSetAttribute((const void*)swap_attn_kernel<DH, WS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  const long long groups = (long long)(a.H / WS) * (a.W / WS) * nchunk;
+  GC_CHECK_ARG(groups < (1LL << 31), "swap attention: too many groups for one launch");
+  swap_attn_klog(DH, WS);
+  swap_attn_kernel<DH, WS><<<dim3((unsigned)groups, a.heads, B), 64 * a.wpc, shm, st>>>(a);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+// out [B][count] = mean over the L rows of x [B][L][count], summed in agent order (count = C * H * W)
+__global__ __launch_bounds__(256) void agent_mean_kernel(const float* __restrict__ x, float* __restrict__ out, int L, long long count) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const float* __restrict__ p = x + (size_t)blockIdx.y * L * count + i;
+  float s = 0.f;
+  for (int l = 0; l < L; ++l) s += p[(size_t)l * count];
+  out[(size_t)blockIdx.y * count + i] = s / (float)L;
+}
+
+}  // namespace gc

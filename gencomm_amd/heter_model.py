@@ -5,7 +5,8 @@ names (= checkpoint keys: ``encoder_m1, backbone_m1, shrinker_m1, message_extrac
 fusion_net, shrink_conv, cls_head, reg_head, dir_head``), same forward order and output dict keys. Every tensor op
 of the forward runs in the HIP library.
 
-Scope: lidar modalities encoded by ``point_pillar`` or ``second``; fusion ``att``, ``max`` or ``v2xvit``.
+Scope: lidar modalities encoded by ``point_pillar`` or ``second``; fusion ``att``, ``max``, ``v2xvit``,
+``where2comm`` or ``cobevt``.
 Camera encoders and the other fusion nets are outside this build and raise ``NotImplementedError`` at
 construction with the yaml key that asked for them.
 
@@ -32,7 +33,7 @@ from .runtime import record_len_list
 from .second import SECOND
 
 _ENCODERS = {"pointpillar": PointPillar, "second": SECOND}  # heter_encoders.py (resolved by lower-cased class name, stage1.py:54-61)
-_OTHER_FUSIONS = ("disconet", "v2vnet", "v2xvit", "cobevt", "where2comm", "who2com")
+_OTHER_FUSIONS = ("disconet", "v2vnet", "who2com")
 
 
 def fix_bn(m):  # opencood/tools/train_utils.py (freeze BatchNorm statistics of fixed modules)
@@ -125,8 +126,11 @@ class HeterModelBaselineWGenComm(nn.Module):
         elif method == "where2comm":
             from .where2comm import Where2commFusion
             self.fusion_net = Where2commFusion(args["where2comm"])  # stage1.py:126-127
+        elif method == "cobevt":
+            from .cobevt import CoBEVT
+            self.fusion_net = CoBEVT(args["cobevt"])  # stage1.py:124-125
         elif method in _OTHER_FUSIONS:
-            raise NotImplementedError(f"fusion_method '{method}' is outside this build ('att', 'max', 'v2xvit' and 'where2comm' are implemented)")
+            raise NotImplementedError(f"fusion_method '{method}' is outside this build ('att', 'max', 'v2xvit', 'where2comm' and 'cobevt' are implemented)")
         else:
             raise ValueError(f"unknown fusion_method '{method}'")
 

@@ -562,6 +562,22 @@ int gencomm_hgt_attn_bwd(const float* qkv, const int* scene_off, const float* do
 long long gencomm_win_attn_bwd_scratch_floats(int n, int heads, int window, int H, int W);
 int gencomm_win_attn_bwd(const float* qkv, const float* pos_embedding, const float* out, const float* dout, float* dqkv, float* dpos,
                          float* scratch, int n, int heads, int dim_head, int window, int H, int W, void* stream);
+/* CoBEVT fusion building blocks (opencood/models/fuse_modules/fusion_in_one.py:409-464, fuse_modules/swap_fusion_modules.py:87-128);
+ * gencomm_amd/cobevt.py is the module with the reference's state_dict keys.
+ *   gencomm_swap_attn_fwd    qkv [B L][3 heads dim_head][H][W] (q | k | v blocks, head-major) -> out [B L][heads dim_head][H][W]: per
+ *                            scene, head and group, attention over the group's L window^2 tokens (agent, w1, w2) jointly:
+ *                            softmax(q k^T / sqrt(dim_head) + bias_table[rel(i, j)][head]) v with rel = the module's
+ *                            relative_position_index, (li - lj + L - 1)(2 window - 1)^2 + (hi - hj + window - 1)(2 window - 1) +
+ *                            (wi - wj + window - 1); bias_table [(2 L - 1)(2 window - 1)^2][heads].  grid_mode 0: a group is the
+ *                            window x window tile (x, y) of the map; 1: the grid cell (x, y), pixels (w1 H / window + x,
+ *                            w2 W / window + y).  num_agents [B] (device): the keys of agents l >= num_agents[b] are masked, the
+ *                            queries of all L agents are computed; values outside 1 .. L are clamped.  window 4 or 8, dim_head 16, 32
+ *                            or 64, L <= 8, H and W multiples of window: anything else is an argument error
+ *   gencomm_agent_mean_fwd   out [B][count] = mean over the L rows of x [B][L][count]
+ * -------------------------------------------------------------------------------------------- */
+int gencomm_swap_attn_fwd(const float* qkv, const float* bias_table, const int* num_agents, float* out, int B, int L, int heads, int dim_head,
+                          int window, int H, int W, int grid_mode, void* stream);
+int gencomm_agent_mean_fwd(const float* x, float* out, int B, int L, long long count, void* stream);
 /* radix-3 split attention over the three window branches (sub_modules/split_attn.py:31-62): out = sum_r softmax_r(fc2(ReLU(LN(fc1(
  * mean_HW(a + b + c))))))[r] * branch_r (+ residual); fc1 [C][C], fc2 [3 C][C] without biases; scratch >= 4 n C floats; C <= 256 */
 int gencomm_split3_attn_fwd(const float* a, const float* b, const float* c, const float* fc1_w, const float* ln_w, const float* ln_b,
