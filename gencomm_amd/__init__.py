@@ -6,6 +6,8 @@ Public surface mirrors the reference's plugin API:
     DiffusionUNet(config)              opencood/models/gencomm_modules/unet.py:198
     Enhancer(C, win_size, num_heads)   opencood/models/gencomm_modules/enhancer.py:359
     AttFusion(feature_dims)            opencood/models/fuse_modules/fusion_in_one.py:126
+    MaxFusion()                        opencood/models/fuse_modules/fusion_in_one.py:87 (fusion_method: max)
+    Who2comFusion(feature_dims)        opencood/models/fuse_modules/fusion_in_one.py:521 (fusion_method: who2com)
     CoBEVT(args)                       opencood/models/fuse_modules/fusion_in_one.py:409 (fusion_method: cobevt; inference)
     regroup, normalize_pairwise_tfm    fusion_in_one.py:48, opencood/utils/transformation_utils.py:68
     MessageExtractorv2(in_ch, out_ch)  opencood/models/gencomm_modules/message_extractor_v2.py:109
@@ -17,11 +19,12 @@ All compute runs in hand-written HIP kernels behind the C ABI of ``include/genco
 from .cobevt import CoBEVT
 from .cond_diff import GenComm
 from .enhancer import Enhancer
-from .fusion import AttFusion, normalize_pairwise_tfm, regroup
+from .fusion import AttFusion, MaxFusion, normalize_pairwise_tfm, regroup
 from .lift_splat_shoot import LiftSplatShoot
 from .message_extractor import MessageExtractorv2
 from .point_pillar_depth_loss import PointPillarDepthLoss
 from .unet import DiffusionUNet
+from .who2com import Who2comFusion
 
 
 
@@ -36,5 +39,5 @@ def set_denoise_dtype(dtype) -> None:
     _lib.check(_lib.lib().gencomm_set_mode(_lib.MODE_ARITH, value), "gencomm_set_mode")
 
 
-__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "CoBEVT", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "regroup", "normalize_pairwise_tfm",
+__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "MaxFusion", "Who2comFusion", "CoBEVT", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "regroup", "normalize_pairwise_tfm",
            "set_denoise_dtype"]

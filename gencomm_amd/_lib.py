@@ -160,6 +160,8 @@ _SIGNATURES = {
     "gencomm_warp_attfuse_bwd_scratch_floats": (_ll, [_i, _i, _i]),
     "gencomm_warp_attfuse_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "gencomm_warp_maxfuse_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "gencomm_warp_maxfuse_bwd_scratch_floats": (_ll, [_i, _i, _i, _i, _i]),
+    "gencomm_warp_maxfuse_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "gencomm_warp_attfuse_tok_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "gencomm_lss_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "gencomm_lss_splat_fwd": (_i, [_p] * 8 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_i)] + [_i] * 6 + [_p, _p, _p, _ll, _p]),

@@ -335,3 +335,21 @@ class AttFusionFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         (xx,) = ctx.saved_tensors
         return None, None, None, ctx.fus._backward_hip(xx, ctx.lens, ctx.affine, grad_out.float().contiguous())
+
+
+class MaxFusionFunction(torch.autograd.Function):
+    """HIP forward (gencomm_warp_maxfuse_fwd) and HIP backward (gencomm_warp_maxfuse_bwd: the winner of every pixel is recomputed with
+    the forward's arithmetic; lowest agent index among equal maxima). No gradient for ``affine_matrix``."""
+
+    @staticmethod
+    def forward(ctx, fus, lens, affine_matrix, xx):
+        with torch.no_grad():
+            out = fus._forward_hip(xx, lens, affine_matrix)
+        ctx.fus, ctx.lens, ctx.affine = fus, list(lens), affine_matrix
+        ctx.save_for_backward(xx)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (xx,) = ctx.saved_tensors
+        return None, None, None, ctx.fus._backward_hip(xx, ctx.lens, ctx.affine, grad_out.float().contiguous())

@@ -23,6 +23,44 @@ struct FuseArgs {
   int mode;              // 0 = ego-row attention (AttFusion), 1 = element-wise max over agents (MaxFusion)
 };
 
+// Bilinear cell of one (output pixel, agent), shared by the forward (both modes) and by the max backward's winner recomputation:
+// float64 affine grid rounded to float32, grid_sampler unnormalize (align_corners=False), the four corners clamped into the map.
+__device__ __forceinline__ void fuse_cell(const double* __restrict__ th, double xb, double yb, int H, int W, int (&idx)[4], unsigned& ok,
+                                          float (&wt)[4]) {
+  const float gx = (float)(th[0] * xb + th[1] * yb + th[2]);
+  const float gy = (float)(th[3] * xb + th[4] * yb + th[5]);
+  // grid_sampler unnormalize (align_corners=False): ((g + 1) * size - 1) / 2
+  const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f;
+  const float iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
+  const float fx = floorf(ix), fy = floorf(iy);
+  // keep the integer conversion in range for far-away agents
+  const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f);
+  const int y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
+  const float tx = ix - fx, ty = iy - fy;  // == ix - ix_nw etc.
+  const float wnw = (1.f - tx) * (1.f - ty), wne = tx * (1.f - ty), wsw = (1.f - tx) * ty, wse = tx * ty;
+  const bool xl = x0 >= 0 && x0 < W, xr = x0 + 1 >= 0 && x0 + 1 < W;
+  const bool yt = y0 >= 0 && y0 < H, yb_ = y0 + 1 >= 0 && y0 + 1 < H;
+  const bool far = fx != (float)x0 || fy != (float)y0;  // clamped => everything out of range
+  // every tap is LOADED, from the corner clamped into the map, and an invalid one is replaced by an exact zero afterwards: with a
+  // branch per tap the loads of a channel were issued one memory latency after the other (the token-major kernel's lesson)
+  const int xc0 = min(max(x0, 0), W - 1), xc1 = min(max(x0 + 1, 0), W - 1), yc0 = min(max(y0, 0), H - 1), yc1 = min(max(y0 + 1, 0), H - 1);
+  idx[0] = yc0 * W + xc0; idx[1] = yc0 * W + xc1; idx[2] = yc1 * W + xc0; idx[3] = yc1 * W + xc1;
+  ok = (xl && yt && !far ? 1u : 0u) | (xr && yt && !far ? 2u : 0u) | (xl && yb_ && !far ? 4u : 0u) | (xr && yb_ && !far ? 8u : 0u);
+  wt[0] = wnw; wt[1] = wne; wt[2] = wsw; wt[3] = wse;
+}
+
+// One warped value: the four taps of a cell, an invalid tap contributing an exact zero (fixed fma order: the max backward recomputes
+// the forward's values bit for bit with this).
+__device__ __forceinline__ float fuse_sample(const float* __restrict__ plane, const int (&idx)[4], unsigned ok, const float (&wt)[4]) {
+  float t[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) t[k] = plane[idx[k]];
+  float v = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v = fmaf((ok >> k) & 1u ? t[k] : 0.f, wt[k], v);
+  return v;
+}
+
 // Workgroup = 64 pixels x 4 channel quarters (wave cq owns channels cq, cq + 4, ...): four times the workgroups and a quarter of the
 // dependent gathers per thread of the one-lane-per-pixel form (2 agents x 128 x 64 x 128: 117 -> see DESIGN section 7); the four partial
 // scores of a pixel meet in LDS.
@@ -39,38 +77,8 @@ __device__ __forceinline__ void fuse_body(const FuseArgs& a, int b, int off, int
   unsigned ok[N];
   float wt[N][4];
 #pragma unroll
-  for (int j = 0; j < N; ++j) {
-    const double* __restrict__ th = a.theta + (size_t)(off + j) * 6;
-    const float gx = (float)(th[0] * xb + th[1] * yb + th[2]);
-    const float gy = (float)(th[3] * xb + th[4] * yb + th[5]);
-    // grid_sampler unnormalize (align_corners=False): ((g + 1) * size - 1) / 2
-    const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f;
-    const float iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
-    const float fx = floorf(ix), fy = floorf(iy);
-    // keep the integer conversion in range for far-away agents
-    const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f);
-    const int y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
-    const float tx = ix - fx, ty = iy - fy;  // == ix - ix_nw etc.
-    const float wnw = (1.f - tx) * (1.f - ty), wne = tx * (1.f - ty), wsw = (1.f - tx) * ty, wse = tx * ty;
-    const bool xl = x0 >= 0 && x0 < W, xr = x0 + 1 >= 0 && x0 + 1 < W;
-    const bool yt = y0 >= 0 && y0 < H, yb_ = y0 + 1 >= 0 && y0 + 1 < H;
-    const bool far = fx != (float)x0 || fy != (float)y0;  // clamped => everything out of range
-    // every tap is LOADED, from the corner clamped into the map, and an invalid one is replaced by an exact zero afterwards: with a
-    // branch per tap the loads of a channel were issued one memory latency after the other (the token-major kernel's lesson)
-    const int xc0 = min(max(x0, 0), W - 1), xc1 = min(max(x0 + 1, 0), W - 1), yc0 = min(max(y0, 0), H - 1), yc1 = min(max(y0 + 1, 0), H - 1);
-    idx[j][0] = yc0 * W + xc0; idx[j][1] = yc0 * W + xc1; idx[j][2] = yc1 * W + xc0; idx[j][3] = yc1 * W + xc1;
-    ok[j] = (xl && yt && !far ? 1u : 0u) | (xr && yt && !far ? 2u : 0u) | (xl && yb_ && !far ? 4u : 0u) | (xr && yb_ && !far ? 8u : 0u);
-    wt[j][0] = wnw; wt[j][1] = wne; wt[j][2] = wsw; wt[j][3] = wse;
-  }
-  auto sample = [&](int j, const float* __restrict__ plane) {
-    float t[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] = plane[idx[j][k]];
-    float v = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v = fmaf((ok[j] >> k) & 1u ? t[k] : 0.f, wt[j][k], v);
-    return v;
-  };
+  for (int j = 0; j < N; ++j) fuse_cell(a.theta + (size_t)(off + j) * 6, xb, yb, H, W, idx[j], ok[j], wt[j]);
+  auto sample = [&](int j, const float* __restrict__ plane) { return fuse_sample(plane, idx[j], ok[j], wt[j]); };
   const float* __restrict__ xs = a.x + (size_t)off * a.C * HW;
   if (a.mode == 1) {  // MaxFusion (fusion_in_one.py:87-124): max over the warped agents, zeros where an agent is out of range
     float* __restrict__ op = a.out + (size_t)b * a.C * HW + pix;
@@ -395,6 +403,35 @@ __global__ __launch_bounds__(64) void fuse_bwd_plan_kernel(const FuseBwdArgs a, 
   }
 }
 
+// Every output pixel p whose bilinear cell (agent transform th) contains the source pixel (qx, qy), with its tap weight: f(p, wgt).
+// Candidates = a window around q's pre-image (float64); each candidate's cell is recomputed with exactly fuse_body's arithmetic.
+// Shared by the gather passes of the attention backward and of the max backward.
+template <class F>
+__device__ __forceinline__ void fuse_for_each_match(const double* __restrict__ th, int qx, int qy, int H, int W, F&& f) {
+  const double gx = (2.0 * qx + 1.0) / (double)W - 1.0, gy = (2.0 * qy + 1.0) / (double)H - 1.0;
+  const double det = th[0] * th[4] - th[1] * th[3];
+  const double xb = (th[4] * (gx - th[2]) - th[1] * (gy - th[5])) / det, yb = (-th[3] * (gx - th[2]) + th[0] * (gy - th[5])) / det;
+  const double pxf = ((xb + 1.0) * W - 1.0) * 0.5, pyf = ((yb + 1.0) * H - 1.0) * 0.5;
+  const int x_lo = max((int)floor(pxf - 1.6), 0), x_hi = min((int)ceil(pxf + 1.6), W - 1);
+  const int y_lo = max((int)floor(pyf - 1.6), 0), y_hi = min((int)ceil(pyf + 1.6), H - 1);
+  for (int py = y_lo; py <= y_hi; ++py)
+    for (int px = x_lo; px <= x_hi; ++px) {
+      const double oxb = (2.0 * px + 1.0) / (double)W - 1.0, oyb = (2.0 * py + 1.0) / (double)H - 1.0;
+      const float sgx = (float)(th[0] * oxb + th[1] * oyb + th[2]);
+      const float sgy = (float)(th[3] * oxb + th[4] * oyb + th[5]);
+      const float ix = ((sgx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((sgy + 1.f) * (float)H - 1.f) * 0.5f;
+      const float fx = floorf(ix), fy = floorf(iy);
+      const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f), y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
+      if (fx != (float)x0 || fy != (float)y0) continue;   // clamped: everything out of range
+      const int dx = qx - x0, dy = qy - y0;
+      if (dx < 0 || dx > 1 || dy < 0 || dy > 1) continue;
+      const float tx = ix - fx, ty = iy - fy;
+      const float wgt = (dx ? tx : 1.f - tx) * (dy ? ty : 1.f - ty);
+      if (wgt == 0.f) continue;
+      f(py * W + px, wgt);
+    }
+}
+
 // d x_j for a non-ego agent without atomics: thread = one SOURCE pixel q of agent j.  The output pixels p whose bilinear cell
 // contains q lie around the pre-image of q; each candidate's cell is recomputed with exactly the forward's arithmetic (float64
 // affine grid cast to float32, floor, clamp), matches are kept in LDS as (p, wt w_j(p), wt d s_j(p)) and then, per channel,
@@ -417,32 +454,7 @@ __global__ __launch_bounds__(128) void fuse_bwd_gather_kernel(const FuseBwdArgs 
   const double* __restrict__ th = a.theta + (size_t)ag * 6;
   int cnt = 0;
   const float2* __restrict__ wsp = reinterpret_cast<const float2*>(a.ws) + (size_t)ag * HW;
-  // every output pixel p whose bilinear cell contains q, with its tap weight: f(p, wgt).  Candidates = a window around q's pre-image
-  // (float64); each candidate's cell is recomputed with exactly fuse_body's arithmetic
-  auto for_each_match = [&](auto&& f) {
-    const double gx = (2.0 * qx + 1.0) / (double)W - 1.0, gy = (2.0 * qy + 1.0) / (double)H - 1.0;
-    const double det = th[0] * th[4] - th[1] * th[3];
-    const double xb = (th[4] * (gx - th[2]) - th[1] * (gy - th[5])) / det, yb = (-th[3] * (gx - th[2]) + th[0] * (gy - th[5])) / det;
-    const double pxf = ((xb + 1.0) * W - 1.0) * 0.5, pyf = ((yb + 1.0) * H - 1.0) * 0.5;
-    const int x_lo = max((int)floor(pxf - 1.6), 0), x_hi = min((int)ceil(pxf + 1.6), W - 1);
-    const int y_lo = max((int)floor(pyf - 1.6), 0), y_hi = min((int)ceil(pyf + 1.6), H - 1);
-    for (int py = y_lo; py <= y_hi; ++py)
-      for (int px = x_lo; px <= x_hi; ++px) {
-        const double oxb = (2.0 * px + 1.0) / (double)W - 1.0, oyb = (2.0 * py + 1.0) / (double)H - 1.0;
-        const float sgx = (float)(th[0] * oxb + th[1] * oyb + th[2]);
-        const float sgy = (float)(th[3] * oxb + th[4] * oyb + th[5]);
-        const float ix = ((sgx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((sgy + 1.f) * (float)H - 1.f) * 0.5f;
-        const float fx = floorf(ix), fy = floorf(iy);
-        const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f), y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
-        if (fx != (float)x0 || fy != (float)y0) continue;   // clamped: everything out of range
-        const int dx = qx - x0, dy = qy - y0;
-        if (dx < 0 || dx > 1 || dy < 0 || dy > 1) continue;
-        const float tx = ix - fx, ty = iy - fy;
-        const float wgt = (dx ? tx : 1.f - tx) * (dy ? ty : 1.f - ty);
-        if (wgt == 0.f) continue;
-        f(py * W + px, wgt);
-      }
-  };
+  auto for_each_match = [&](auto&& f) { fuse_for_each_match(th, qx, qy, H, W, f); };
   if (live) {
     for_each_match([&](int p, float wgt) {
       if (cnt < FUSE_KM) {
@@ -514,6 +526,161 @@ inline int warp_attfuse_bwd_enqueue(const float* x, const double* theta, const i
   }
   warp_attfuse_bwd_kernel<<<dim3((H * W + 63) / 64, B), 256, 0, st>>>(a);
   fuse_bwd_gather_kernel<<<dim3((H * W + 127) / 128, n), 128, 0, st>>>(a, B);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Backward of warp + element-wise max over the agents (MaxFusion, fusion_in_one.py:87-124: torch.max(neighbor_feature, dim=0)[0]).
+// Nothing is kept by the forward: per (scene, channel, output pixel) the winner is RECOMPUTED with the forward's own device functions
+// (fuse_cell / fuse_sample: same cells, same fma order, so the same bits) and is the LOWEST agent index among the maxima -- what
+// torch.max(dim=0) returns on the CPU and where value_selecting_reduction_backward sends the gradient; a NaN wins, the first NaN first.
+// Ties are the common case here (every agent that misses a pixel contributes an exact 0, post-ReLU maps are full of zeros).
+//   d x_j[c][q] = sum_p [winner(c, p) = j] tap_weight_j(p, q) g[c][p]
+// Paths, decided per agent by fuse_bwd_plan_kernel (the attention backward's plan, unchanged):
+//   ego with an identity warp     its own pixel, written once by the pixel pass
+//   tame non-ego agents           maxfuse_bwd_gather_kernel: thread = source pixel, reads the one-byte winner map the pixel pass wrote
+//                                 ([B][C][HW]: C HW bytes per scene against N C HW 4 bytes of re-gathering every agent per candidate);
+//                                 no float atomics, every element written exactly once: two runs are bit-identical
+//   anything else / no scratch    the pixel pass scatters the winner's four taps with float atomics into the zeroed grad_x
+// ---------------------------------------------------------------------------------------------
+struct MaxBwdArgs {
+  const float* x;        // [n][C][H][W] forward input
+  const double* theta;   // [n][2][3]
+  const int* scene_off;  // [B+1]
+  const float* gout;     // [B][C][H][W]
+  float* gx;             // [n][C][H][W], zeroed by the enqueue
+  int C, H, W;
+  unsigned char* win;    // scratch [B][C][HW]: winner of (scene, channel, output pixel) as an agent index inside the scene; null = no gather
+  const int* plan;       // scratch [n] written by fuse_bwd_plan_kernel; null = every agent scatters
+};
+
+template <int N>
+__device__ __forceinline__ void maxfuse_bwd_body(const MaxBwdArgs& a, int b, int off, int pix, int cq) {
+  const int H = a.H, W = a.W, HW = H * W;
+  if (pix >= HW) return;   // no barrier in this kernel
+  const int h = pix / W, w = pix - h * W;
+  const double xb = (2.0 * w + 1.0) / (double)W - 1.0;
+  const double yb = (2.0 * h + 1.0) / (double)H - 1.0;
+  int idx[N][4];
+  unsigned ok[N];
+  float wt[N][4];
+  int gat[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    fuse_cell(a.theta + (size_t)(off + j) * 6, xb, yb, H, W, idx[j], ok[j], wt[j]);
+    gat[j] = a.plan != nullptr ? a.plan[off + j] : 0;
+  }
+  const float* __restrict__ xs = a.x + (size_t)off * a.C * HW;
+  const float* __restrict__ gp = a.gout + (size_t)b * a.C * HW + pix;
+  float* __restrict__ gxs = a.gx + (size_t)off * a.C * HW;
+  for (int c = cq; c < a.C; c += 4) {
+    float best = fuse_sample(xs + (size_t)c * HW, idx[0], ok[0], wt[0]);
+    int wi = 0;
+#pragma unroll
+    for (int j = 1; j < N; ++j) {
+      const float v = fuse_sample(xs + ((size_t)j * a.C + c) * HW, idx[j], ok[j], wt[j]);
+      // torch's max: strictly greater replaces (the first of equal values stays), a NaN replaces anything but an earlier NaN
+      if (!(best != best) && (v > best || v != v)) { best = v; wi = j; }
+    }
+    const float g = gp[(size_t)c * HW];
+    if (a.win != nullptr) a.win[((size_t)b * a.C + c) * HW + pix] = (unsigned char)wi;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {   // unrolled with a predicate: idx / wt stay in registers (no dynamic index)
+      if (j != wi) continue;
+      float* __restrict__ plane = gxs + ((size_t)j * a.C + c) * HW;
+      if (gat[j] == 1) {
+        if (j == 0) plane[pix] = g;   // identity ego: its own pixel, exactly once
+        continue;                     // tame non-ego: the gather pass
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (((ok[j] >> k) & 1u) && wt[j][k] != 0.f) atomicAdd(plane + idx[j][k], wt[j][k] * g);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void warp_maxfuse_bwd_kernel(const MaxBwdArgs a) {
+  const int b = blockIdx.y;
+  const int off = a.scene_off[b], N = a.scene_off[b + 1] - off;   // block-uniform
+  const int pl = threadIdx.x & 63, cq = threadIdx.x >> 6;
+  const int pix = blockIdx.x * 64 + pl;
+  switch (N) {
+    case 1: maxfuse_bwd_body<1>(a, b, off, pix, cq); break;
+    case 2: maxfuse_bwd_body<2>(a, b, off, pix, cq); break;
+    case 3: maxfuse_bwd_body<3>(a, b, off, pix, cq); break;
+    case 4: maxfuse_bwd_body<4>(a, b, off, pix, cq); break;
+    case 5: maxfuse_bwd_body<5>(a, b, off, pix, cq); break;
+    case 6: maxfuse_bwd_body<6>(a, b, off, pix, cq); break;
+    case 7: maxfuse_bwd_body<7>(a, b, off, pix, cq); break;
+    case 8: maxfuse_bwd_body<8>(a, b, off, pix, cq); break;
+    default: break;   // the plan kernel sent such a scene to the scatter and nothing is scattered: its gradients stay zero
+  }
+}
+
+// d x_j of a tame non-ego agent: thread = one SOURCE pixel q; the output pixels whose cell contains q are found once (LDS), then per
+// channel the tap weights of those that agent j WON are summed in a fixed order.
+__global__ __launch_bounds__(128) void maxfuse_bwd_gather_kernel(const MaxBwdArgs a, int B) {
+  __shared__ int s_p[FUSE_KM][128];
+  __shared__ float s_w[FUSE_KM][128];
+  const int ag = blockIdx.y, tid = threadIdx.x;
+  if (a.plan[ag] != 1) return;
+  int b = 0;
+  while (b + 1 < B && a.scene_off[b + 1] <= ag) ++b;
+  const int off = a.scene_off[b];
+  if (ag == off) return;                 // the ego: written by the pixel pass
+  const int me = ag - off;               // 1 .. 7: the byte the pixel pass wrote where this agent won
+  const int H = a.H, W = a.W, HW = H * W;
+  const int q = blockIdx.x * 128 + tid;
+  const bool live = q < HW;
+  const int qy = live ? q / W : 0, qx = live ? q - qy * W : 0;
+  const double* __restrict__ th = a.theta + (size_t)ag * 6;
+  int cnt = 0;
+  if (live) {
+    fuse_for_each_match(th, qx, qy, H, W, [&](int p, float wgt) {
+      if (cnt < FUSE_KM) { s_p[cnt][tid] = p; s_w[cnt][tid] = wgt; }
+      ++cnt;
+    });
+  }
+  const bool overflow = cnt > FUSE_KM;   // as in fuse_bwd_gather_kernel: the rest is found again per channel, never dropped
+  const int kept = min(cnt, FUSE_KM);
+  const float* __restrict__ gp = a.gout + (size_t)b * a.C * HW;
+  const unsigned char* __restrict__ wp = a.win + (size_t)b * a.C * HW;
+  float* __restrict__ out = a.gx + (size_t)ag * a.C * HW + q;
+  for (int c = 0; c < a.C; ++c) {
+    float acc = 0.f;
+    for (int k = 0; k < kept; ++k) {
+      const int p = s_p[k][tid];
+      const float g = gp[(size_t)c * HW + p];
+      if (wp[(size_t)c * HW + p] == me) acc = fmaf(s_w[k][tid], g, acc);
+    }
+    if (overflow) {
+      int m = 0;
+      fuse_for_each_match(th, qx, qy, H, W, [&](int p, float wgt) {
+        if (m++ >= FUSE_KM && wp[(size_t)c * HW + p] == me) acc = fmaf(wgt, gp[(size_t)c * HW + p], acc);
+      });
+    }
+    if (live) out[(size_t)c * HW] = acc;
+  }
+}
+
+// scratch layout (floats): [winner bytes, B C HW rounded up to whole floats][plan: n ints][64 spare, as the attention backward keeps]
+inline size_t warp_maxfuse_bwd_win_floats(int B, int C, int H, int W) { return ((size_t)B * C * H * W + 3) / 4; }
+inline size_t warp_maxfuse_bwd_scratch_floats(int B, int n, int C, int H, int W) { return warp_maxfuse_bwd_win_floats(B, C, H, W) + (size_t)n + 64; }
+// scratch: warp_maxfuse_bwd_scratch_floats(B, n, C, H, W) floats, or null -- every agent then takes the scatter with float atomics
+inline int warp_maxfuse_bwd_enqueue(const float* x, const double* theta, const int* scene_off, const float* gout, float* gx, float* scratch,
+                                    int B, int n, int C, int H, int W, hipStream_t st) {
+  GC_HIP(hipMemsetAsync(gx, 0, (size_t)n * C * H * W * sizeof(float), st));
+  MaxBwdArgs a{x, theta, scene_off, gout, gx, C, H, W, nullptr, nullptr};
+  if (scratch != nullptr) {
+    int* plan = reinterpret_cast<int*>(scratch + warp_maxfuse_bwd_win_floats(B, C, H, W));
+    FuseBwdArgs pa{x, theta, scene_off, gout, gx, C, H, W, nullptr, plan};   // the plan reads theta, scene_off, H, W and writes plan
+    fuse_bwd_plan_kernel<<<(B + 63) / 64, 64, 0, st>>>(pa, B);
+    a.win = reinterpret_cast<unsigned char*>(scratch);
+    a.plan = plan;
+  }
+  warp_maxfuse_bwd_kernel<<<dim3((H * W + 63) / 64, B), 256, 0, st>>>(a);
+  if (scratch != nullptr) maxfuse_bwd_gather_kernel<<<dim3((H * W + 127) / 128, n), 128, 0, st>>>(a, B);
   GC_HIP(hipGetLastError());
   return GC_OK;
 }

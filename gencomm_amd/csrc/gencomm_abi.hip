@@ -1185,6 +1185,18 @@ int gencomm_warp_maxfuse_fwd(const float* x, const double* theta, const int* sce
   return warp_attfuse_enqueue(x, theta, scene_off, out, B, n, C, H, W, (hipStream_t)stream, 1);
 }
 
+long long gencomm_warp_maxfuse_bwd_scratch_floats(int B, int n, int C, int H, int W) {
+  if (B < 1 || n < B || C < 1 || H < 1 || W < 1) { fail(GC_ERR_ARG, "bad B/n/C/H/W"); return -1; }
+  return (long long)warp_maxfuse_bwd_scratch_floats(B, n, C, H, W);
+}
+int gencomm_warp_maxfuse_bwd(const float* x, const double* theta, const int* scene_off, const float* grad_out, float* grad_x, float* scratch,
+                             int B, int n, int C, int H, int W, void* stream) {
+  GC_CHECK_ARG(x && theta && scene_off && grad_out && grad_x, "null pointer");   // scratch may be null: every agent then scatters
+  GC_CHECK_ARG(B >= 1 && B <= 65535 && n >= B && n <= 65535 && C >= 1 && H >= 1 && W >= 1, "bad B/n/C/H/W");
+  GC_CHECK_ARG((long long)H * W < (1LL << 31), "H*W too large");
+  return warp_maxfuse_bwd_enqueue(x, theta, scene_off, grad_out, grad_x, scratch, B, n, C, H, W, (hipStream_t)stream);
+}
+
 int gencomm_warp_attfuse_tok_fwd(const void* enhancer_workspace, const double* theta, const int* scene_off, float* out,
                                  int B, int n, int C, int H, int W, void* stream) {
   EnhancerPlan p;

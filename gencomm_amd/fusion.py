@@ -104,8 +104,9 @@ class AttFusion(nn.Module):
 
 
 class MaxFusion(AttFusion):
-    """fusion_in_one.py:87-124: warp every agent to the ego frame, element-wise max over the agents (inference path;
-    no autograd)."""
+    """fusion_in_one.py:87-124: warp every agent to the ego frame, element-wise max over the agents. With gradients enabled and an
+    input that requires one the call goes through ``autograd.MaxFusionFunction`` (HIP forward, HIP backward
+    ``gencomm_warp_maxfuse_bwd``: the gradient of a pixel goes to the lowest-indexed agent among its maxima, as torch.max's does)."""
     _entry = "gencomm_warp_maxfuse_fwd"
 
     def __init__(self):
@@ -113,9 +114,26 @@ class MaxFusion(AttFusion):
 
     def forward(self, x, record_len, affine_matrix):
         require_gpu(x, "MaxFusion.forward")
-        if torch.is_grad_enabled() and x.requires_grad:
-            raise NotImplementedError("MaxFusion: backward is not implemented on the HIP path")
         lens = record_len_list(record_len)
         if len(lens) != affine_matrix.shape[0] or sum(lens) != x.shape[0] or min(lens) < 1 or max(lens) > MAX_AGENTS_PER_SCENE:
             raise ValueError(f"record_len {lens} inconsistent with input / 1..{MAX_AGENTS_PER_SCENE} agents per scene")
+        if torch.is_grad_enabled() and x.requires_grad:
+            from .autograd import MaxFusionFunction  # HIP forward and HIP backward
+            return MaxFusionFunction.apply(self, lens, affine_matrix, f32c(x))
         return self._forward_hip(f32c(x), lens, affine_matrix)
+
+    def _backward_hip(self, xx, lens, affine_matrix, grad_out):
+        n, C, H, W = xx.shape
+        B = affine_matrix.shape[0]
+        theta = gather_ego_thetas(affine_matrix, lens).to(xx.device)
+        off = [0]
+        for k in lens:
+            off.append(off[-1] + k)
+        scene_off = dev_ints(off, xx.device)
+        gx = torch.empty_like(xx)
+        l = _lib.lib()
+        scratch = torch.empty(_lib.check_size(l.gencomm_warp_maxfuse_bwd_scratch_floats(B, n, C, H, W), "gencomm_warp_maxfuse_bwd_scratch_floats"),
+                              dtype=torch.float32, device=xx.device)
+        _lib.check(l.gencomm_warp_maxfuse_bwd(ptr(xx), ptr(theta), ptr(scene_off), ptr(grad_out), ptr(gx), ptr(scratch), B, n, C, H, W,
+                                              stream_ptr(xx.device)), "gencomm_warp_maxfuse_bwd")
+        return gx

@@ -6,7 +6,7 @@ fusion_net, shrink_conv, cls_head, reg_head, dir_head``), same forward order and
 of the forward runs in the HIP library.
 
 Scope: lidar modalities encoded by ``point_pillar`` or ``second``; fusion ``att``, ``max``, ``v2xvit``,
-``where2comm`` or ``cobevt``.
+``where2comm``, ``cobevt`` or ``who2com``.
 Camera encoders and the other fusion nets are outside this build and raise ``NotImplementedError`` at
 construction with the yaml key that asked for them.
 
@@ -33,7 +33,7 @@ from .runtime import record_len_list
 from .second import SECOND
 
 _ENCODERS = {"pointpillar": PointPillar, "second": SECOND}  # heter_encoders.py (resolved by lower-cased class name, stage1.py:54-61)
-_OTHER_FUSIONS = ("disconet", "v2vnet", "who2com")
+_OTHER_FUSIONS = ("disconet", "v2vnet")   # disconet: the reference itself cannot build it
 
 
 def fix_bn(m):  # opencood/tools/train_utils.py (freeze BatchNorm statistics of fixed modules)
@@ -129,8 +129,11 @@ class HeterModelBaselineWGenComm(nn.Module):
         elif method == "cobevt":
             from .cobevt import CoBEVT
             self.fusion_net = CoBEVT(args["cobevt"])  # stage1.py:124-125
+        elif method == "who2com":
+            from .who2com import Who2comFusion
+            self.fusion_net = Who2comFusion(args["who2com"])  # stage1.py:127-128 (the block itself is the channel count)
         elif method in _OTHER_FUSIONS:
-            raise NotImplementedError(f"fusion_method '{method}' is outside this build ('att', 'max', 'v2xvit', 'where2comm' and 'cobevt' are implemented)")
+            raise NotImplementedError(f"fusion_method '{method}' is outside this build ('att', 'max', 'v2xvit', 'where2comm', 'cobevt' and 'who2com' are implemented)")
         else:
             raise ValueError(f"unknown fusion_method '{method}'")
 

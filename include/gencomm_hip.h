@@ -418,6 +418,16 @@ int gencomm_warp_attfuse_bwd(const float* x, const double* theta, const int* sce
 int gencomm_warp_maxfuse_fwd(const float* x, const double* theta, const int* scene_off, float* out,
                              int B, int n, int C, int H, int W, void* stream);
 
+/* Backward of gencomm_warp_maxfuse_fwd (torch.max(dim=0) over the warped agents + F.grid_sample): grad_x [n][C][H][W] is OVERWRITTEN.
+ * The winner of every (scene, channel, output pixel) is recomputed with the forward's arithmetic; among equal maxima the LOWEST agent
+ * index wins (torch's CPU rule; exact ties are common: agents that miss a pixel contribute 0), a NaN wins, the first NaN first.
+ * scratch: gencomm_warp_maxfuse_bwd_scratch_floats(B, n, C, H, W) floats (a one-byte winner map [B][C][H W] and the per-agent plan).
+ * Path per agent as in gencomm_warp_attfuse_bwd: identity ego written once per pixel, rigid-like agents gathered per source pixel
+ * (no float atomics: two runs are bit-identical), anything else scattered with float atomics; scratch == NULL: every agent scatters. */
+long long gencomm_warp_maxfuse_bwd_scratch_floats(int B, int n, int C, int H, int W);
+int gencomm_warp_maxfuse_bwd(const float* x, const double* theta, const int* scene_off, const float* grad_out, float* grad_x, float* scratch,
+                             int B, int n, int C, int H, int W, void* stream);
+
 /* Fast lane for callers that chain Enhancer -> fusion themselves (ScenePipeline): call
  * gencomm_enhancer_fwd with out == NULL (the token-major result and the channel gate stay in the
  * workspace, the NHWC->NCHW transpose launch is skipped), then this entry point with the SAME
