@@ -9,6 +9,7 @@ Public surface mirrors the reference's plugin API:
     MaxFusion()                        opencood/models/fuse_modules/fusion_in_one.py:87 (fusion_method: max)
     Who2comFusion(feature_dims)        opencood/models/fuse_modules/fusion_in_one.py:521 (fusion_method: who2com)
     CoBEVT(args)                       opencood/models/fuse_modules/fusion_in_one.py:409 (fusion_method: cobevt; inference)
+    V2VNetFusion(args)                 opencood/models/fuse_modules/fusion_in_one.py:238 (the v2vnet block; a component, inference)
     regroup, normalize_pairwise_tfm    fusion_in_one.py:48, opencood/utils/transformation_utils.py:68
     MessageExtractorv2(in_ch, out_ch)  opencood/models/gencomm_modules/message_extractor_v2.py:109
     LiftSplatShoot(args)               opencood/models/heter_encoders.py:83 (camera_encoder: Resnet101; trainable=True trains it)
@@ -24,6 +25,7 @@ from .lift_splat_shoot import LiftSplatShoot
 from .message_extractor import MessageExtractorv2
 from .point_pillar_depth_loss import PointPillarDepthLoss
 from .unet import DiffusionUNet
+from .v2vnet import V2VNetFusion
 from .who2com import Who2comFusion
 
 
@@ -39,5 +41,5 @@ def set_denoise_dtype(dtype) -> None:
     _lib.check(_lib.lib().gencomm_set_mode(_lib.MODE_ARITH, value), "gencomm_set_mode")
 
 
-__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "MaxFusion", "Who2comFusion", "CoBEVT", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "regroup", "normalize_pairwise_tfm",
+__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "MaxFusion", "Who2comFusion", "CoBEVT", "V2VNetFusion", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "regroup", "normalize_pairwise_tfm",
            "set_denoise_dtype"]

@@ -113,6 +113,9 @@ _SIGNATURES = {
     "gencomm_win_attn_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "gencomm_swap_attn_fwd": (_i, [_p, _p, _p, _p] + [_i] * 8 + [_p]),
     "gencomm_agent_mean_fwd": (_i, [_p, _p, _i, _i, _ll, _p]),
+    "gencomm_v2v_warp_pairs_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "gencomm_v2v_aggregate_fwd": (_i, [_p] * 7 + [_i] * 6 + [_p]),
+    "gencomm_gru_gate_fwd": (_i, [_p, _p, _i, _i, _i, _p]),
     "gencomm_iou3d_pairwise_fwd": (_i, [_p, _i, _p, _i, _i, _p, _p]),
     "gencomm_iou3d_max_boxes": (_i, []),
     "gencomm_iou3d_nms_workspace_bytes": (_ll, [_i]),

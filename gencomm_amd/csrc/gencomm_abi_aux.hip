@@ -1,6 +1,6 @@
 // Second translation unit of libgencomm_hip.so: iou3d_nms (reference extension semantics), the point-cloud voxeliser,
 // the V2X-ViT attention kernels, the sparse 3-D convolutions of the SECOND encoder, the Lift-Splat-Shoot camera encoder
-// the training-time anchor target assignment, the batched lidar front end and CoBEVT's swap attention.
+// the training-time anchor target assignment, the batched lidar front end, CoBEVT's swap attention and V2VNet's message passing.
 // Kept apart from gencomm_abi.hip so that the rocPRIM templates do not lengthen the hot path's compile.
 #include "../../include/gencomm_hip.h"
 
@@ -13,6 +13,7 @@
 #include "sparse_kernels.h"
 #include "swap_attn_kernels.h"
 #include "target_kernels.h"
+#include "v2v_kernels.h"
 #include "v2xvit_kernels.h"
 #include "voxel_batch_kernels.h"
 #include "voxel_kernels.h"
@@ -196,6 +197,65 @@ int gencomm_agent_mean_fwd(const float* x, float* out, int B, int L, long long c
   GC_CHECK_ARG(x && out, "null pointer");
   GC_CHECK_ARG(B >= 1 && B <= 65535 && L >= 1 && count >= 1 && (count + 255) / 256 < (1LL << 31), "agent mean: bad B / L / count");
   agent_mean_kernel<<<dim3((unsigned)((count + 255) / 256), B), 256, 0, (hipStream_t)stream>>>(x, out, L, count);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+// ---- V2VNet message passing (v2v_kernels.h) ------------------------------------------------------------------------------
+int gencomm_v2v_warp_pairs_fwd(const float* x, const double* theta, const int* src_row, float* out, int P, int C, int H, int W, void* stream) {
+  GC_CHECK_ARG(x && theta && src_row && out, "null pointer");
+  GC_CHECK_ARG(P >= 1 && P <= 65535 && C >= 1 && H >= 1 && W >= 1, "v2v warp pairs: 1..65535 pairs, positive C / H / W");
+  GC_CHECK_ARG((long long)C * H * W < (1LL << 31), "v2v warp pairs: one agent's map must stay below 2^31 elements");
+  V2vWarpArgs a{x, theta, src_row, out, C, H, W};
+  GC_KLOG("v2v_warp_pairs_kernel");
+  v2v_warp_pairs_kernel<<<dim3((H * W + 63) / 64, P), 256, 0, (hipStream_t)stream>>>(a);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_v2v_aggregate_fwd(const float* y, const float* e, const float* h, const double* theta, const int* node_row, const int* pair_off,
+                              float* out, int n_nodes, int C, int H, int W, int op, int out_mode, void* stream) {
+  GC_CHECK_ARG(y && e && h && theta && node_row && pair_off && out, "null pointer");
+  GC_CHECK_ARG(n_nodes >= 1 && n_nodes <= 65535 && C >= 1 && H >= 1 && W >= 1, "v2v aggregate: 1..65535 nodes, positive C / H / W");
+  GC_CHECK_ARG(op == 0 || op == 1, "v2v aggregate: op must be 0 (mean) or 1 (max)");
+  GC_CHECK_ARG(out_mode == 0 || out_mode == 1, "v2v aggregate: out_mode must be 0 ([h | agg]) or 1 (h + agg)");
+  GC_CHECK_ARG((long long)2 * C * H * W < (1LL << 31), "v2v aggregate: one node's [h | agg] map must stay below 2^31 elements");
+  const int HW = H * W;
+  const bool vec = HW % 4 == 0 && (((uintptr_t)y | (uintptr_t)e | (uintptr_t)h | (uintptr_t)out) & 15) == 0;
+  const int px = vec ? 256 : 64;                                   // pixels per workgroup
+  const int gx = (HW + px - 1) / px;
+  // channel slices (blockIdx.z) until the launch has about four workgroups per compute unit; a slice keeps at least 16 channels, so the
+  // masks a workgroup computes serve at least four channels per thread
+  int cpb = (C + 3) / 4 * 4;
+  while (cpb >= 32 && (long long)gx * n_nodes * ((C + cpb - 1) / cpb) < 1024) cpb = (cpb / 2 + 3) / 4 * 4;
+  const int gz = (C + cpb - 1) / cpb;
+  GC_CHECK_ARG(gz <= 65535, "v2v aggregate: too many channels");
+  V2vAggArgs a{y, e, h, theta, node_row, pair_off, out, C, H, W, op, out_mode, cpb};
+  hipStream_t st = (hipStream_t)stream;
+  if (vec) {
+    GC_KLOG("v2v_aggregate_kernel<4>");
+    v2v_aggregate_kernel<4><<<dim3(gx, n_nodes, gz), 256, 0, st>>>(a);
+  } else {
+    GC_KLOG("v2v_aggregate_kernel<1>");
+    v2v_aggregate_kernel<1><<<dim3(gx, n_nodes, gz), 256, 0, st>>>(a);
+  }
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_gru_gate_fwd(const float* g, float* h, int n, int C, int HW, void* stream) {
+  GC_CHECK_ARG(g && h, "null pointer");
+  GC_CHECK_ARG(n >= 1 && n <= 65535 && C >= 1 && HW >= 1, "gru gate: 1..65535 rows, positive C / HW");
+  const long long count = (long long)C * HW;
+  GC_CHECK_ARG(count < (1LL << 31), "gru gate: one row must stay below 2^31 elements");
+  hipStream_t st = (hipStream_t)stream;
+  if (count % 4 == 0 && (((uintptr_t)g | (uintptr_t)h) & 15) == 0) {
+    GC_KLOG("gru_gate_kernel<4>");
+    gru_gate_kernel<4><<<dim3((unsigned)((count / 4 + 255) / 256), n), 256, 0, st>>>(g, h, count);
+  } else {
+    GC_KLOG("gru_gate_kernel<1>");
+    gru_gate_kernel<1><<<dim3((unsigned)((count + 255) / 256), n), 256, 0, st>>>(g, h, count);
+  }
   GC_HIP(hipGetLastError());
   return GC_OK;
 }

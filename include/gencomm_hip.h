@@ -588,6 +588,23 @@ int gencomm_win_attn_bwd(const float* qkv, const float* pos_embedding, const flo
 int gencomm_swap_attn_fwd(const float* qkv, const float* bias_table, const int* num_agents, float* out, int B, int L, int heads, int dim_head,
                           int window, int H, int W, int grid_mode, void* stream);
 int gencomm_agent_mean_fwd(const float* x, float* out, int B, int L, long long count, void* stream);
+/* V2VNet fusion building blocks (opencood/models/fuse_modules/fusion_in_one.py:238-353, sub_modules/convgru.py); gencomm_amd/v2vnet.py is
+ * the module with the reference's state_dict keys. The convolutions between them run through gencomm_conv2d_fwd.
+ *   gencomm_v2v_warp_pairs_fwd  out[p] = warp_affine_simple(x[src_row[p]], theta[p]) for P (target, source) pairs; x [rows][C][H][W] is
+ *                               read in place, theta [P][2][3] float64, src_row [P] (device; rows outside x are NOT detected). A pair
+ *                               whose theta is exactly the identity is copied
+ *   gencomm_v2v_aggregate_fwd   node k of n_nodes owns the pairs pair_off[k] .. pair_off[k + 1] - 1 (1..8 of them; a node with another
+ *                               count is left UNTOUCHED, pair_off lives on the device) and the state h[node_row[k]]:
+ *                               m_p = (y[p] + e[k]) * mask_p with mask_p = the warp of a map of ones under theta[p], computed in the
+ *                               kernel; agg = mean_p m_p (op 0, divisor = the number of pairs) or max_p m_p (op 1, fmaxf);
+ *                               out_mode 0: out [n_nodes][2 C][H][W] = [h | agg], out_mode 1: out [n_nodes][C][H][W] = h + agg
+ *   gencomm_gru_gate_fwd        h [n][C][HW] = sigmoid(g[n][c]) * tanh(g[n][C + c]) over g [n][2 C][HW]: a ConvGRU cell whose hidden
+ *                               state is zero (g = the convolution with the stacked [update-gate; candidate] weights)
+ * -------------------------------------------------------------------------------------------- */
+int gencomm_v2v_warp_pairs_fwd(const float* x, const double* theta, const int* src_row, float* out, int P, int C, int H, int W, void* stream);
+int gencomm_v2v_aggregate_fwd(const float* y, const float* e, const float* h, const double* theta, const int* node_row, const int* pair_off,
+                              float* out, int n_nodes, int C, int H, int W, int op, int out_mode, void* stream);
+int gencomm_gru_gate_fwd(const float* g, float* h, int n, int C, int HW, void* stream);
 /* radix-3 split attention over the three window branches (sub_modules/split_attn.py:31-62): out = sum_r softmax_r(fc2(ReLU(LN(fc1(
  * mean_HW(a + b + c))))))[r] * branch_r (+ residual); fc1 [C][C], fc2 [3 C][C] without biases; scratch >= 4 n C floats; C <= 256 */
 int gencomm_split3_attn_fwd(const float* a, const float* b, const float* c, const float* fc1_w, const float* ln_w, const float* ln_b,
