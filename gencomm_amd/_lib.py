@@ -85,6 +85,8 @@ _SIGNATURES = {
     "gencomm_conv2d_wgrad": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "gencomm_conv2d_wgrad_scratch_floats": (_ll, [_i] * 8),
     "gencomm_conv2d_wgrad_ws": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p]),
+    "gencomm_conv2d_wgrad_fixed_scratch_floats": (_ll, [_i] * 6),
+    "gencomm_conv2d_wgrad_fixed": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _ll, _p]),
     "gencomm_gn_nchw_fwd": (_i, [_p, _p, _p, _p, _p, C.c_float, _i, _i, _i, _i, _i, _p]),
     "gencomm_ln_nchw_fwd": (_i, [_p, _p, _p, _p, C.c_float, _i, _i, _i, _i, _p]),
     "gencomm_ln_nchw_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, C.c_float, _i, _i, _i, _i, _p]),
@@ -116,6 +118,11 @@ _SIGNATURES = {
     "gencomm_v2v_warp_pairs_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "gencomm_v2v_aggregate_fwd": (_i, [_p] * 7 + [_i] * 6 + [_p]),
     "gencomm_gru_gate_fwd": (_i, [_p, _p, _i, _i, _i, _p]),
+    "gencomm_gru_gate_bwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "gencomm_v2v_aggregate_train_fwd": (_i, [_p] * 8 + [_i] * 6 + [_p]),
+    "gencomm_v2v_aggregate_bwd": (_i, [_p] * 7 + [_i] * 6 + [_p]),
+    "gencomm_v2v_warp_pairs_bwd_scratch_floats": (_ll, [_i]),
+    "gencomm_v2v_warp_pairs_bwd": (_i, [_p] * 7 + [_i] * 6 + [_p]),
     "gencomm_iou3d_pairwise_fwd": (_i, [_p, _i, _p, _i, _i, _p, _p]),
     "gencomm_iou3d_max_boxes": (_i, []),
     "gencomm_iou3d_nms_workspace_bytes": (_ll, [_i]),

@@ -353,3 +353,30 @@ class MaxFusionFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         (xx,) = ctx.saved_tensors
         return None, None, None, ctx.fus._backward_hip(xx, ctx.lens, ctx.affine, grad_out.float().contiguous())
+
+
+class V2VNetFunction(torch.autograd.Function):
+    """``V2VNetFusion(args, trainable=True)``: the HIP forward with the training aggregation entry (the same output bits as inference)
+    and the HIP backward of ``V2VNetFusion._backward_hip`` (gencomm_gru_gate_bwd, gencomm_v2v_aggregate_bwd, gencomm_v2v_warp_pairs_bwd
+    around the convolution's input- and weight-gradient kernels). Gradients for ``x`` and the parameters, none for ``affine_matrix``."""
+
+    @staticmethod
+    def forward(ctx, fus, lens, affine_matrix, names, x, *params):
+        from .runtime import f32c
+        rounds = []
+        with torch.no_grad():
+            out = fus._forward_hip(f32c(x), list(lens), affine_matrix, rounds)
+        ctx.fus, ctx.names, ctx.rounds = fus, names, rounds
+        ctx.save_for_backward(*params)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        params = ctx.saved_tensors
+        w = {n: p.detach().float() for n, p in zip(ctx.names, params)}
+        need = {n: bool(ctx.needs_input_grad[5 + i]) for i, n in enumerate(ctx.names)}
+        if not ctx.fus.gru_flag:                      # the ConvGRU is not run: its parameters get no gradient at all
+            need = {n: v and not n.startswith("conv_gru.") for n, v in need.items()}
+        with torch.no_grad():
+            dx, grads = ctx.fus._backward_hip(ctx.rounds, w, need, bool(ctx.needs_input_grad[4]), grad_out.float().contiguous())
+        return (None, None, None, None, dx, *[grads.get(n) for n in ctx.names])

@@ -44,4 +44,36 @@ __device__ __forceinline__ float fuse_sample(const float* __restrict__ plane, co
   return v;
 }
 
+// The most matches a gather pass keeps per source pixel (fuse_bwd_plan_kernel's bound for a tame transform).
+constexpr int FUSE_KM = 12;
+
+// Every output pixel p whose bilinear cell (agent transform th) contains the source pixel (qx, qy), with its tap weight: f(p, wgt).
+// Candidates = a window around q's pre-image (float64); each candidate's cell is recomputed with exactly fuse_body's arithmetic.
+// Shared by the gather passes of the attention backward and of the max backward.
+template <class F>
+__device__ __forceinline__ void fuse_for_each_match(const double* __restrict__ th, int qx, int qy, int H, int W, F&& f) {
+  const double gx = (2.0 * qx + 1.0) / (double)W - 1.0, gy = (2.0 * qy + 1.0) / (double)H - 1.0;
+  const double det = th[0] * th[4] - th[1] * th[3];
+  const double xb = (th[4] * (gx - th[2]) - th[1] * (gy - th[5])) / det, yb = (-th[3] * (gx - th[2]) + th[0] * (gy - th[5])) / det;
+  const double pxf = ((xb + 1.0) * W - 1.0) * 0.5, pyf = ((yb + 1.0) * H - 1.0) * 0.5;
+  const int x_lo = max((int)floor(pxf - 1.6), 0), x_hi = min((int)ceil(pxf + 1.6), W - 1);
+  const int y_lo = max((int)floor(pyf - 1.6), 0), y_hi = min((int)ceil(pyf + 1.6), H - 1);
+  for (int py = y_lo; py <= y_hi; ++py)
+    for (int px = x_lo; px <= x_hi; ++px) {
+      const double oxb = (2.0 * px + 1.0) / (double)W - 1.0, oyb = (2.0 * py + 1.0) / (double)H - 1.0;
+      const float sgx = (float)(th[0] * oxb + th[1] * oyb + th[2]);
+      const float sgy = (float)(th[3] * oxb + th[4] * oyb + th[5]);
+      const float ix = ((sgx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((sgy + 1.f) * (float)H - 1.f) * 0.5f;
+      const float fx = floorf(ix), fy = floorf(iy);
+      const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f), y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
+      if (fx != (float)x0 || fy != (float)y0) continue;   // clamped: everything out of range
+      const int dx = qx - x0, dy = qy - y0;
+      if (dx < 0 || dx > 1 || dy < 0 || dy > 1) continue;
+      const float tx = ix - fx, ty = iy - fy;
+      const float wgt = (dx ? tx : 1.f - tx) * (dy ? ty : 1.f - ty);
+      if (wgt == 0.f) continue;
+      f(py * W + px, wgt);
+    }
+}
+
 }  // namespace gc

@@ -337,7 +337,6 @@ __device__ __forceinline__ void fuse_bwd_body(const FuseBwdArgs& a, int b, int o
 // of a scene): 1 if its warp is exactly the identity -- d x_0 is then written once per pixel without atomics.  Others: 1 if the
 // inverse map is tame (in pixel units every row of its matrix has an L1 norm <= 1.5, true for the rigid transforms of
 // normalize_pairwise_tfm): at most KM output pixels sample a source pixel and they lie in a 5 x 5 window around its pre-image.
-constexpr int FUSE_KM = 12;
 __global__ __launch_bounds__(64) void fuse_bwd_plan_kernel(const FuseBwdArgs a, int B) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
@@ -364,35 +363,6 @@ __global__ __launch_bounds__(64) void fuse_bwd_plan_kernel(const FuseBwdArgs a, 
     }
     a.plan[off + j] = ok;
   }
-}
-
-// Every output pixel p whose bilinear cell (agent transform th) contains the source pixel (qx, qy), with its tap weight: f(p, wgt).
-// Candidates = a window around q's pre-image (float64); each candidate's cell is recomputed with exactly fuse_body's arithmetic.
-// Shared by the gather passes of the attention backward and of the max backward.
-template <class F>
-__device__ __forceinline__ void fuse_for_each_match(const double* __restrict__ th, int qx, int qy, int H, int W, F&& f) {
-  const double gx = (2.0 * qx + 1.0) / (double)W - 1.0, gy = (2.0 * qy + 1.0) / (double)H - 1.0;
-  const double det = th[0] * th[4] - th[1] * th[3];
-  const double xb = (th[4] * (gx - th[2]) - th[1] * (gy - th[5])) / det, yb = (-th[3] * (gx - th[2]) + th[0] * (gy - th[5])) / det;
-  const double pxf = ((xb + 1.0) * W - 1.0) * 0.5, pyf = ((yb + 1.0) * H - 1.0) * 0.5;
-  const int x_lo = max((int)floor(pxf - 1.6), 0), x_hi = min((int)ceil(pxf + 1.6), W - 1);
-  const int y_lo = max((int)floor(pyf - 1.6), 0), y_hi = min((int)ceil(pyf + 1.6), H - 1);
-  for (int py = y_lo; py <= y_hi; ++py)
-    for (int px = x_lo; px <= x_hi; ++px) {
-      const double oxb = (2.0 * px + 1.0) / (double)W - 1.0, oyb = (2.0 * py + 1.0) / (double)H - 1.0;
-      const float sgx = (float)(th[0] * oxb + th[1] * oyb + th[2]);
-      const float sgy = (float)(th[3] * oxb + th[4] * oyb + th[5]);
-      const float ix = ((sgx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((sgy + 1.f) * (float)H - 1.f) * 0.5f;
-      const float fx = floorf(ix), fy = floorf(iy);
-      const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f), y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
-      if (fx != (float)x0 || fy != (float)y0) continue;   // clamped: everything out of range
-      const int dx = qx - x0, dy = qy - y0;
-      if (dx < 0 || dx > 1 || dy < 0 || dy > 1) continue;
-      const float tx = ix - fx, ty = iy - fy;
-      const float wgt = (dx ? tx : 1.f - tx) * (dy ? ty : 1.f - ty);
-      if (wgt == 0.f) continue;
-      f(py * W + px, wgt);
-    }
 }
 
 // d x_j for a non-ego agent without atomics: thread = one SOURCE pixel q of agent j.  The output pixels p whose bilinear cell

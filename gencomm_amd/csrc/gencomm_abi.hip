@@ -778,6 +778,30 @@ int gencomm_conv2d_wgrad_ws(const float* dy, const float* x, float* dw, float* d
   WgradArgs a{dy, x, nullptr, dw, db, Cout, Cin, 0, Ho, Wo, Hi, Wi, K, stride, pad, 0};
   return conv_wgrad_enqueue(a, N, (hipStream_t)stream);
 }
+// The weight gradient with a FIXED order of additions (two runs give the same bits): stride 1, pad = K / 2. Wide 3x3 layers take the
+// split-K kernel with its partial sums and fixed-order reduction; every other shape (1x1 layers of any width included) takes the
+// 8 x 8-channel-chunk kernel with one partial-sum record per workgroup and a single reducing slice.
+static bool wgrad_fixed_wide(int Cin, int Cout, int K) { return K == 3 && Cin >= 32 && Cout >= 32; }
+long long gencomm_conv2d_wgrad_fixed_scratch_floats(int N, int Cin, int Hi, int Wi, int Cout, int K) {
+  if (!(N >= 1 && Cin >= 1 && Cout >= 1 && Hi >= 1 && Wi >= 1 && (K == 1 || K == 3))) {
+    fail(GC_ERR_ARG, "gencomm_conv2d_wgrad_fixed_scratch_floats: bad dims");
+    return -1;
+  }
+  if (wgrad_fixed_wide(Cin, Cout, K)) return (long long)wgrad3x3_wide_scratch_floats(N, Cin, Cout, Hi, Wi, 1);
+  return (long long)conv_wgrad_scratch_floats(Cout, Cin, K, Hi, Wi, N);
+}
+int gencomm_conv2d_wgrad_fixed(const float* dy, const float* x, float* dw, float* db, int N, int Cin, int Hi, int Wi, int Cout, int K,
+                               float* scratch, long long scratch_floats, void* stream) {
+  GC_CHECK_ARG(dy && x && dw && scratch, "null pointer");
+  const long long need = gencomm_conv2d_wgrad_fixed_scratch_floats(N, Cin, Hi, Wi, Cout, K);
+  if (need < 0) return GC_ERR_ARG;
+  GC_CHECK_ARG(scratch_floats >= need, "scratch smaller than gencomm_conv2d_wgrad_fixed_scratch_floats");
+  GC_CHECK_ARG(N <= 65535, "wgrad fixed: too many samples");
+  if (wgrad_fixed_wide(Cin, Cout, K)) return wgrad3x3_wide_enqueue(dy, x, dw, db, N, Cin, Hi, Wi, Cout, Hi, Wi, 1, 1, scratch, (hipStream_t)stream);
+  WgradArgs a{dy, x, nullptr, dw, db, Cout, Cin, 0, Hi, Wi, Hi, Wi, K, 1, K / 2, 0};
+  a.part = scratch;
+  return conv_wgrad_enqueue(a, N, (hipStream_t)stream, true);
+}
 int gencomm_conv2d_wgrad(const float* dy, const float* x, float* dw, float* db, int N, int Cin, int Hi, int Wi, int Cout,
                          int K, int stride, int pad, void* stream) {
   return gencomm_conv2d_wgrad_ws(dy, x, dw, db, N, Cin, Hi, Wi, Cout, K, stride, pad, nullptr, 0, stream);

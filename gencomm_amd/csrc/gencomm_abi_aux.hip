@@ -213,15 +213,18 @@ int gencomm_v2v_warp_pairs_fwd(const float* x, const double* theta, const int* s
   return GC_OK;
 }
 
-int gencomm_v2v_aggregate_fwd(const float* y, const float* e, const float* h, const double* theta, const int* node_row, const int* pair_off,
-                              float* out, int n_nodes, int C, int H, int W, int op, int out_mode, void* stream) {
+// The inference entry (winner == nullptr, train == false) and the training entry share the checks and the launch geometry.
+static int v2v_aggregate_enqueue(const float* y, const float* e, const float* h, const double* theta, const int* node_row, const int* pair_off,
+                                 float* out, unsigned char* winner, bool train, int n_nodes, int C, int H, int W, int op, int out_mode,
+                                 void* stream) {
   GC_CHECK_ARG(y && e && h && theta && node_row && pair_off && out, "null pointer");
   GC_CHECK_ARG(n_nodes >= 1 && n_nodes <= 65535 && C >= 1 && H >= 1 && W >= 1, "v2v aggregate: 1..65535 nodes, positive C / H / W");
   GC_CHECK_ARG(op == 0 || op == 1, "v2v aggregate: op must be 0 (mean) or 1 (max)");
   GC_CHECK_ARG(out_mode == 0 || out_mode == 1, "v2v aggregate: out_mode must be 0 ([h | agg]) or 1 (h + agg)");
   GC_CHECK_ARG((long long)2 * C * H * W < (1LL << 31), "v2v aggregate: one node's [h | agg] map must stay below 2^31 elements");
   const int HW = H * W;
-  const bool vec = HW % 4 == 0 && (((uintptr_t)y | (uintptr_t)e | (uintptr_t)h | (uintptr_t)out) & 15) == 0;
+  GC_CHECK_ARG(!train || op == 0 || winner != nullptr, "v2v aggregate: the training entry needs the winner map for op 1 (max)");
+  const bool vec = HW % 4 == 0 && (((uintptr_t)y | (uintptr_t)e | (uintptr_t)h | (uintptr_t)out) & 15) == 0 && ((uintptr_t)winner & 3) == 0;
   const int px = vec ? 256 : 64;                                   // pixels per workgroup
   const int gx = (HW + px - 1) / px;
   // channel slices (blockIdx.z) until the launch has about four workgroups per compute unit; a slice keeps at least 16 channels, so the
@@ -230,15 +233,90 @@ int gencomm_v2v_aggregate_fwd(const float* y, const float* e, const float* h, co
   while (cpb >= 32 && (long long)gx * n_nodes * ((C + cpb - 1) / cpb) < 1024) cpb = (cpb / 2 + 3) / 4 * 4;
   const int gz = (C + cpb - 1) / cpb;
   GC_CHECK_ARG(gz <= 65535, "v2v aggregate: too many channels");
-  V2vAggArgs a{y, e, h, theta, node_row, pair_off, out, C, H, W, op, out_mode, cpb};
+  V2vAggArgs a{y, e, h, theta, node_row, pair_off, out, C, H, W, op, out_mode, cpb, winner};
   hipStream_t st = (hipStream_t)stream;
-  if (vec) {
+  const dim3 grid(gx, n_nodes, gz);
+  // The mean keeps no winner: the training entry then launches the inference instantiation itself (the same code object, so the same
+  // bits by construction). For the max, `out` is a product folded with fmaxf in both instantiations: nothing the compiler could contract.
+  if (train && op == 1) {
+    GC_KLOG(vec ? "v2v_aggregate_kernel<4, train>" : "v2v_aggregate_kernel<1, train>");
+    if (vec) v2v_aggregate_kernel<4, true><<<grid, 256, 0, st>>>(a);
+    else v2v_aggregate_kernel<1, true><<<grid, 256, 0, st>>>(a);
+  } else if (vec) {
     GC_KLOG("v2v_aggregate_kernel<4>");
-    v2v_aggregate_kernel<4><<<dim3(gx, n_nodes, gz), 256, 0, st>>>(a);
+    v2v_aggregate_kernel<4, false><<<grid, 256, 0, st>>>(a);
   } else {
     GC_KLOG("v2v_aggregate_kernel<1>");
-    v2v_aggregate_kernel<1><<<dim3(gx, n_nodes, gz), 256, 0, st>>>(a);
+    v2v_aggregate_kernel<1, false><<<grid, 256, 0, st>>>(a);
   }
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_v2v_aggregate_fwd(const float* y, const float* e, const float* h, const double* theta, const int* node_row, const int* pair_off,
+                              float* out, int n_nodes, int C, int H, int W, int op, int out_mode, void* stream) {
+  return v2v_aggregate_enqueue(y, e, h, theta, node_row, pair_off, out, nullptr, false, n_nodes, C, H, W, op, out_mode, stream);
+}
+
+int gencomm_v2v_aggregate_train_fwd(const float* y, const float* e, const float* h, const double* theta, const int* node_row, const int* pair_off,
+                                    float* out, unsigned char* winner, int n_nodes, int C, int H, int W, int op, int out_mode, void* stream) {
+  return v2v_aggregate_enqueue(y, e, h, theta, node_row, pair_off, out, winner, true, n_nodes, C, H, W, op, out_mode, stream);
+}
+
+int gencomm_v2v_aggregate_bwd(const float* dout, const double* theta, const int* node_row, const int* pair_off, const unsigned char* winner,
+                              float* dy, float* de, int n_nodes, int C, int H, int W, int op, int out_mode, void* stream) {
+  (void)node_row;   // the pass-through gradient of h is a slice of dout: no kernel touches the rows
+  GC_CHECK_ARG(dout && theta && pair_off && dy && de, "null pointer");
+  GC_CHECK_ARG(n_nodes >= 1 && n_nodes <= 65535 && C >= 1 && H >= 1 && W >= 1, "v2v aggregate backward: 1..65535 nodes, positive C / H / W");
+  GC_CHECK_ARG(op == 0 || op == 1, "v2v aggregate backward: op must be 0 (mean) or 1 (max)");
+  GC_CHECK_ARG(out_mode == 0 || out_mode == 1, "v2v aggregate backward: out_mode must be 0 ([h | agg]) or 1 (h + agg)");
+  GC_CHECK_ARG(op == 0 || winner != nullptr, "v2v aggregate backward: op 1 (max) needs the winner map of gencomm_v2v_aggregate_train_fwd");
+  GC_CHECK_ARG((long long)2 * C * H * W < (1LL << 31), "v2v aggregate backward: one node's [h | agg] map must stay below 2^31 elements");
+  const int HW = H * W;
+  const float* dagg = out_mode == 0 ? dout + (size_t)C * HW : dout;
+  const size_t node_stride = (size_t)(out_mode == 0 ? 2 * C : C) * HW;
+  const bool vec = HW % 4 == 0 && (((uintptr_t)dagg | (uintptr_t)dy | (uintptr_t)de) & 15) == 0 && ((uintptr_t)winner & 3) == 0;
+  const int px = vec ? 256 : 64;
+  const int gx = (HW + px - 1) / px;
+  int cpb = (C + 3) / 4 * 4;                                       // the forward's channel slices
+  while (cpb >= 32 && (long long)gx * n_nodes * ((C + cpb - 1) / cpb) < 1024) cpb = (cpb / 2 + 3) / 4 * 4;
+  const int gz = (C + cpb - 1) / cpb;
+  GC_CHECK_ARG(gz <= 65535, "v2v aggregate backward: too many channels");
+  V2vAggBwdArgs a{dagg, node_stride, theta, pair_off, winner, dy, de, C, H, W, op, cpb};
+  hipStream_t st = (hipStream_t)stream;
+  GC_KLOG(vec ? "v2v_aggregate_bwd_kernel<4>" : "v2v_aggregate_bwd_kernel<1>");
+  if (vec) v2v_aggregate_bwd_kernel<4><<<dim3(gx, n_nodes, gz), 256, 0, st>>>(a);
+  else v2v_aggregate_bwd_kernel<1><<<dim3(gx, n_nodes, gz), 256, 0, st>>>(a);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+long long gencomm_v2v_warp_pairs_bwd_scratch_floats(int P) {
+  if (P < 1 || P > 65535) { fail(GC_ERR_ARG, "v2v warp pairs backward: 1..65535 pairs"); return -1; }
+  return (long long)P + 64;
+}
+
+int gencomm_v2v_warp_pairs_bwd(const float* dwarped, const double* theta, const int* src_row, const int* row_pair_off, const int* row_pairs,
+                               float* dx, float* scratch, int P, int rows, int C, int H, int W, int accumulate, void* stream) {
+  GC_CHECK_ARG(dwarped && theta && src_row && row_pair_off && row_pairs && dx && scratch, "null pointer");
+  GC_CHECK_ARG(P >= 1 && P <= 65535 && rows >= 1 && rows <= 65535 && C >= 1 && H >= 1 && W >= 1,
+               "v2v warp pairs backward: 1..65535 pairs and rows, positive C / H / W");
+  GC_CHECK_ARG(accumulate == 0 || accumulate == 1, "v2v warp pairs backward: accumulate must be 0 or 1");
+  GC_CHECK_ARG((long long)C * H * W < (1LL << 31), "v2v warp pairs backward: one agent's map must stay below 2^31 elements");
+  const int HW = H * W;
+  const int gx = (HW + 63) / 64;
+  // channel slices (blockIdx.z) until the launch has about 1024 workgroups; a slice keeps at least 16 channels, so the match lists a
+  // workgroup builds serve at least four channels per thread
+  int cpb = (C + 3) / 4 * 4;
+  while (cpb >= 32 && (long long)gx * rows * ((C + cpb - 1) / cpb) < 1024) cpb = (cpb / 2 + 3) / 4 * 4;
+  const int gz = (C + cpb - 1) / cpb;
+  GC_CHECK_ARG(gz <= 65535, "v2v warp pairs backward: too many channels");
+  V2vWarpBwdArgs a{dwarped, theta, src_row, row_pair_off, row_pairs, dx, reinterpret_cast<int*>(scratch), P, C, H, W, accumulate, cpb};
+  hipStream_t st = (hipStream_t)stream;
+  GC_KLOG("v2v_warp_bwd_gather_kernel");
+  v2v_warp_bwd_plan_kernel<<<(P + 63) / 64, 64, 0, st>>>(a);
+  v2v_warp_bwd_gather_kernel<<<dim3(gx, rows, gz), 256, 0, st>>>(a);
+  v2v_warp_bwd_scatter_kernel<<<dim3(gx, P), 256, 0, st>>>(a);   // a workgroup whose pair was gathered leaves at once
   GC_HIP(hipGetLastError());
   return GC_OK;
 }
@@ -255,6 +333,23 @@ int gencomm_gru_gate_fwd(const float* g, float* h, int n, int C, int HW, void* s
   } else {
     GC_KLOG("gru_gate_kernel<1>");
     gru_gate_kernel<1><<<dim3((unsigned)((count + 255) / 256), n), 256, 0, st>>>(g, h, count);
+  }
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_gru_gate_bwd(const float* g, const float* dh, float* dg, int n, int C, int HW, void* stream) {
+  GC_CHECK_ARG(g && dh && dg, "null pointer");
+  GC_CHECK_ARG(n >= 1 && n <= 65535 && C >= 1 && HW >= 1, "gru gate backward: 1..65535 rows, positive C / HW");
+  const long long count = (long long)C * HW;
+  GC_CHECK_ARG(count < (1LL << 31), "gru gate backward: one row must stay below 2^31 elements");
+  hipStream_t st = (hipStream_t)stream;
+  if (count % 4 == 0 && (((uintptr_t)g | (uintptr_t)dh | (uintptr_t)dg) & 15) == 0) {
+    GC_KLOG("gru_gate_bwd_kernel<4>");
+    gru_gate_bwd_kernel<4><<<dim3((unsigned)((count / 4 + 255) / 256), n), 256, 0, st>>>(g, dh, dg, count);
+  } else {
+    GC_KLOG("gru_gate_bwd_kernel<1>");
+    gru_gate_bwd_kernel<1><<<dim3((unsigned)((count + 255) / 256), n), 256, 0, st>>>(g, dh, dg, count);
   }
   GC_HIP(hipGetLastError());
   return GC_OK;

@@ -543,8 +543,12 @@ inline size_t conv_wgrad_scratch_floats(int Cout, int Cin, int K, int H, int W, 
   return (size_t)((H + 15) / 16) * ((W + 31) / 32) * n * ((Cout + 7) / 8) * ((Cin + 7) / 8) * NT * 128;
 }
 
-inline int conv_wgrad_enqueue(const WgradArgs& a, int n, hipStream_t st) {
+// fixed_order (needs a.part): every workgroup writes its partial sums and ONE slice adds them in workgroup order, so that two runs give the
+// same bits; without it the workgroups, or the 16 slices of the second stage, meet in dw with float atomics.
+inline int conv_wgrad_enqueue(const WgradArgs& a, int n, hipStream_t st, bool fixed_order = false) {
   const int Cin = a.c0 + a.c1;
+  if (fixed_order && !(a.part != nullptr && a.stride == 1 && (a.K == 3 || a.K == 1) && a.pad == a.K / 2 && a.Ho == a.Hi && a.Wo == a.Wi))
+    return fail(GC_ERR_ARG, "conv_wgrad: the fixed-order form needs scratch and a stride-1 layer with pad = K / 2");
   if (a.stride == 1 && (a.K == 3 || a.K == 1) && a.pad == a.K / 2 && a.Ho == a.Hi && a.Wo == a.Wi) {   // fp32 matrix cores
     const int tiles = ((a.Ho + 15) / 16) * ((a.Wo + 31) / 32);
     const long long pairs = (long long)((a.Cout + 7) / 8) * ((Cin + 7) / 8);
@@ -557,11 +561,11 @@ inline int conv_wgrad_enqueue(const WgradArgs& a, int n, hipStream_t st) {
     // into dw -- kWgradDirectMaxWg-way contention per address at most, what the second stage's 16 slices already have -- and the second
     // launch (a third of this layer's backward launches) is not issued.  Larger maps keep the partial sums + reduce.
     const int nwg = (int)(grid.x * grid.z);
-    if (nwg <= kWgradDirectMaxWg) b.part = nullptr;
+    if (nwg <= kWgradDirectMaxWg && !fixed_order) b.part = nullptr;
     if (a.K == 3) conv_wgrad_mfma_kernel<3><<<grid, 256, 0, st>>>(b);
     else conv_wgrad_mfma_kernel<1><<<grid, 256, 0, st>>>(b);
     if (b.part != nullptr) {
-      const int slices = std::min(nwg, 16), per = (nwg + slices - 1) / slices;
+      const int slices = fixed_order ? 1 : std::min(nwg, 16), per = (nwg + slices - 1) / slices;
       const int NW = ((8 * a.K * a.K + 1 + 15) / 16) * 128;
       const dim3 rg((NW + 255) / 256, grid.y, (nwg + per - 1) / per);
       if (a.K == 3) conv_wgrad_reduce_kernel<3><<<rg, 256, 0, st>>>(a, nwg, per);

@@ -90,6 +90,23 @@ def conv2d_wgrad(dy: torch.Tensor, x: torch.Tensor, k: int, pad: int, bias: bool
     return dw, db
 
 
+def conv2d_wgrad_fixed(dy: torch.Tensor, x: torch.Tensor, k: int, bias: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """`conv2d_wgrad` for a stride-1 layer with pad = k // 2, with a fixed order of additions (gencomm_conv2d_wgrad_fixed: partial sums
+    in scratch, one reducing pass, no float atomics between workgroups): two runs give the same bits."""
+    dy, x = _c(dy), _c(x)
+    n, cout = dy.shape[:2]
+    cin, H, W = x.shape[1:]
+    l = _lib.lib()
+    blob = pool_zeros(cout * cin * k * k + (cout if bias else 0), torch.float32, x.device)
+    dw = blob[:cout * cin * k * k].view(cout, cin, k, k)
+    db = blob[cout * cin * k * k:] if bias else None
+    need = _lib.check_size(l.gencomm_conv2d_wgrad_fixed_scratch_floats(n, cin, H, W, cout, k), "gencomm_conv2d_wgrad_fixed_scratch_floats")
+    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=x.device)
+    _lib.check(l.gencomm_conv2d_wgrad_fixed(ptr(dy), ptr(x), ptr(dw), ptr(db), n, cin, H, W, cout, k, ptr(scratch), need, stream_ptr(x.device)),
+               "gencomm_conv2d_wgrad_fixed")
+    return dw, db
+
+
 def stem7x7_wgrad(dy: torch.Tensor, x: torch.Tensor, cout: int) -> torch.Tensor:
     """Weight gradient [cout, cin, 7, 7] of a 7x7 stride-2 pad-3 convolution (cin <= 3, cout a multiple of 64: the ResNet stem) from
     dy [n, cout, Ho, Wo] and x [n, cin, H, W]: partial sums over pixel ranges, added in a fixed order (no atomics)."""

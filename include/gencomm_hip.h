@@ -455,6 +455,13 @@ int gencomm_conv2d_wgrad(const float* dy, const float* x, float* dw, float* db, 
  * (Cin, Cout >= 32: the BEV backbone, opencood/models/sub_modules/base_bev_backbone.py:40-92) then store per-workgroup partial sums and
  * add them in a fixed order -- deterministic, and 10x faster than the f32 atomics of the scratch-less form on 256-channel layers. */
 long long gencomm_conv2d_wgrad_scratch_floats(int N, int Cin, int Hi, int Wi, int Cout, int K, int stride, int pad);
+/* The same gradient (dw, db +=; stride 1, pad = K / 2, K = 1 or 3) with a FIXED order of additions: every workgroup writes its partial
+ * sums into scratch (gencomm_conv2d_wgrad_fixed_scratch_floats(...) floats, required) and one pass adds them in workgroup order, so two
+ * runs give the same bits. gencomm_conv2d_wgrad / _ws meet in dw with float atomics for every shape but the wide 3x3 one with scratch.
+ * The V2VNet training path uses this form. */
+long long gencomm_conv2d_wgrad_fixed_scratch_floats(int N, int Cin, int Hi, int Wi, int Cout, int K);
+int gencomm_conv2d_wgrad_fixed(const float* dy, const float* x, float* dw, float* db, int N, int Cin, int Hi, int Wi, int Cout, int K,
+                               float* scratch, long long scratch_floats, void* stream);
 int gencomm_conv2d_wgrad_ws(const float* dy, const float* x, float* dw, float* db, int N, int Cin, int Hi, int Wi, int Cout,
                             int K, int stride, int pad, float* scratch, long long scratch_floats, void* stream);
 /* GroupNorm (+ SiLU when silu != 0) over NCHW for any channel count and group size (unet.py:36-37, :31-33): the general-width
@@ -605,6 +612,35 @@ int gencomm_v2v_warp_pairs_fwd(const float* x, const double* theta, const int* s
 int gencomm_v2v_aggregate_fwd(const float* y, const float* e, const float* h, const double* theta, const int* node_row, const int* pair_off,
                               float* out, int n_nodes, int C, int H, int W, int op, int out_mode, void* stream);
 int gencomm_gru_gate_fwd(const float* g, float* h, int n, int C, int HW, void* stream);
+/* Training of the V2VNet fusion (gencomm_amd/v2vnet.py, trainable=True): the adjoints of the three entries above. No float atomics
+ * except where noted; every output element is written exactly once, zeros included.
+ *   gencomm_gru_gate_bwd             dg [n][2 C][HW] from g and dh [n][C][HW]: dg[:C] = dh tanh(c) s (1 - s), dg[C:] = dh s (1 - tanh(c)^2),
+ *                                    s = sigmoid(g[:C]) and c = g[C:] recomputed
+ *   gencomm_v2v_aggregate_train_fwd  gencomm_v2v_aggregate_fwd (the same bits in `out`) which for op 1 also writes winner [n_nodes][C][H][W]:
+ *                                    the index, within the node's pairs, of the winning message under torch.max's rule (a strictly greater
+ *                                    value replaces the current one: the lowest index among equal maxima; a NaN replaces anything but an
+ *                                    earlier NaN). winner may be null for op 0
+ *   gencomm_v2v_aggregate_bwd        dagg = the second channel half of dout [n_nodes][2 C][H][W] (out_mode 0) or dout [n_nodes][C][H][W]
+ *                                    itself (out_mode 1); d m_p = dagg / N_k (op 0) or dagg [winner == p] (op 1);
+ *                                    dy [P][C][H][W] = d m_p mask_p, de [n_nodes][C][H][W] = sum_p d m_p mask_p, the masks recomputed as in
+ *                                    the forward. A node with a pair count outside 1..8 is left UNTOUCHED. The gradient of h is a slice of
+ *                                    dout (out_mode 0) or dout (out_mode 1): node_row is not read
+ *   gencomm_v2v_warp_pairs_bwd       dx[r] (+)= sum over the pairs p with src_row[p] == r of the adjoint of the bilinear warp of
+ *                                    dwarped[p] under theta[p]; dx [rows][C][H][W]; row_pair_off [rows + 1] / row_pairs [P] (device) list the
+ *                                    pairs by source row. accumulate 1 adds into dx, 0 overwrites every element (a row that no pair reads
+ *                                    becomes zero). Per pair, decided on the device: an exactly-identity theta is an addition, a tame theta
+ *                                    (L1 row norms of the inverse pixel-space matrix <= 1.5, |det| > 0.6: every rigid transform) is gathered
+ *                                    per source pixel -- with such pairs only, two runs are bit-identical -- and anything else is scattered
+ *                                    WITH FLOAT ATOMICS afterwards. scratch: gencomm_v2v_warp_pairs_bwd_scratch_floats(P) floats
+ * -------------------------------------------------------------------------------------------- */
+int gencomm_gru_gate_bwd(const float* g, const float* dh, float* dg, int n, int C, int HW, void* stream);
+int gencomm_v2v_aggregate_train_fwd(const float* y, const float* e, const float* h, const double* theta, const int* node_row, const int* pair_off,
+                                    float* out, unsigned char* winner, int n_nodes, int C, int H, int W, int op, int out_mode, void* stream);
+int gencomm_v2v_aggregate_bwd(const float* dout, const double* theta, const int* node_row, const int* pair_off, const unsigned char* winner,
+                              float* dy, float* de, int n_nodes, int C, int H, int W, int op, int out_mode, void* stream);
+long long gencomm_v2v_warp_pairs_bwd_scratch_floats(int P);
+int gencomm_v2v_warp_pairs_bwd(const float* dwarped, const double* theta, const int* src_row, const int* row_pair_off, const int* row_pairs,
+                               float* dx, float* scratch, int P, int rows, int C, int H, int W, int accumulate, void* stream);
 /* radix-3 split attention over the three window branches (sub_modules/split_attn.py:31-62): out = sum_r softmax_r(fc2(ReLU(LN(fc1(
  * mean_HW(a + b + c))))))[r] * branch_r (+ residual); fc1 [C][C], fc2 [3 C][C] without biases; scratch >= 4 n C floats; C <= 256 */
 int gencomm_split3_attn_fwd(const float* a, const float* b, const float* c, const float* fc1_w, const float* ln_w, const float* ln_b,
