@@ -578,6 +578,7 @@ inline int conv2d_enqueue(const Conv2dArgs& a, int N, int KH, int KW, hipStream_
     const int tiles3 = ((a.Ho + 3) / 4) * ((a.Wo + 15) / 16);
     const dim3 g3(tiles3, (a.CoutP + 63) / 64, N);
     if (g3.y > 65535 || g3.z > 65535) return fail(GC_ERR_ARG, "conv2d: too many channel tiles / samples");
+    GC_KLOG(a.stride == 1 ? "conv3x3_f16s_kernel<1>" : "conv3x3_f16s_kernel<2>");
     if (a.stride == 1) conv3x3_f16s_kernel<1><<<g3, 256, 0, st>>>(a);
     else conv3x3_f16s_kernel<2><<<g3, 256, 0, st>>>(a);
     GC_HIP(hipGetLastError());
@@ -591,6 +592,7 @@ inline int conv2d_enqueue(const Conv2dArgs& a, int N, int KH, int KW, hipStream_
     const bool narrow = (long long)((HW + 63) / 64) * mb * N < 1024;  // fewer than 4 workgroups per CU: halve the pixel tile
     const dim3 g1(narrow ? (HW + 31) / 32 : (HW + 63) / 64, mb, N);
     if (g1.y > 65535 || g1.z > 65535) return fail(GC_ERR_ARG, "conv2d: too many channel tiles / samples");
+    GC_KLOG(narrow ? "conv1x1_f16s_kernel<32>" : "conv1x1_f16s_kernel<64>");
     if (narrow) conv1x1_f16s_kernel<32><<<g1, 256, 0, st>>>(a);
     else conv1x1_f16s_kernel<64><<<g1, 256, 0, st>>>(a);
     GC_HIP(hipGetLastError());

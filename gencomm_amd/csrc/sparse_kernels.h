@@ -458,11 +458,13 @@ inline int sp_conv_enqueue(const SpConvArgs& a, hipStream_t st) {
   if (a.K > 32) return fail(GC_ERR_ARG, "sparse conv: at most 32 kernel offsets (3 x 3 x 3)");
   const dim3 grid((a.n_out + 63) / 64, (a.CoutP + 63) / 64);
   if (modes_snapshot().split2() && (a.Cin == 32 || a.Cin == 64)) {
+    GC_KLOG(a.Cin == 32 ? "sp_conv_f16s_kernel<32>" : "sp_conv_f16s_kernel<64>");
     if (a.Cin == 32) sp_conv_f16s_kernel<32><<<grid, 256, 0, st>>>(a);
     else sp_conv_f16s_kernel<64><<<grid, 256, 0, st>>>(a);
     GC_HIP(hipGetLastError());
     return GC_OK;
   }
+  GC_KLOG(a.Cin <= 4 ? "sp_conv_kernel<4>" : a.Cin <= 16 ? "sp_conv_kernel<16>" : a.Cin <= 32 ? "sp_conv_kernel<32>" : "sp_conv_kernel<64>");
   if (a.Cin <= 4) sp_conv_kernel<4><<<grid, 256, 0, st>>>(a);
   else if (a.Cin <= 16) sp_conv_kernel<16><<<grid, 256, 0, st>>>(a);
   else if (a.Cin <= 32) sp_conv_kernel<32><<<grid, 256, 0, st>>>(a);

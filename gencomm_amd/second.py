@@ -25,6 +25,7 @@ from .runtime import f32c, ptr, require_gpu, stream_ptr, workspaces
 from .train_ops import bn_batch_statistics, check_batch_size
 
 
+_NO_KEY = 0x7FFFFFFFFFFFFFFF  # csrc/sparse_kernels.h kSpNoKey: the key of a voxel outside the grid (sorts last)
 TRACE = None  # tools/second_bench.py sets a list here to collect (Cin, Cout, rulebook) per layer for the FLOP count
 
 
@@ -290,12 +291,13 @@ class _DenseFn(torch.autograd.Function):
     def backward(ctx, g):
         sp = ctx.sp
         D, H, W = sp.shape
-        k = sp.keys
+        live = sp.keys != _NO_KEY                  # rows without a key (out-of-grid voxels) were not scattered: gradient 0
+        k = torch.where(live, sp.keys, torch.zeros_like(sp.keys))
         xx = k % W
         yy = (k // W) % H
         zz = (k // (W * H)) % D
         bb = k // (W * H * D)
-        return g[bb, :, zz, yy, xx].contiguous(), None
+        return (g[bb, :, zz, yy, xx] * live.unsqueeze(1)).contiguous(), None
 
 
 def _run(seq: nn.Sequential, x: SparseTensor) -> SparseTensor:
@@ -322,8 +324,10 @@ class MeanVFE(nn.Module):  # mean_vfe.py:4-33
         require_gpu(v, "MeanVFE")
         v = f32c(v)
         n, P, F = v.shape
-        out = torch.empty(n, F, dtype=torch.float32, device=v.device)
         perm = batch_dict.get('_sorted_perm')
+        if perm is not None:
+            n = int(perm.shape[0])                               # one output row per sorted row (voxels outside the grid are left out)
+        out = torch.empty(n, F, dtype=torch.float32, device=v.device)
         _lib.check(_lib.lib().gencomm_mean_vfe_fwd(ptr(v), ptr(k.to(torch.int32).contiguous()), ptr(perm) if perm is not None else None, ptr(out),
                                                    n, P, F, stream_ptr(v.device)), "gencomm_mean_vfe_fwd")
         batch_dict['voxel_features'] = out
@@ -410,8 +414,17 @@ class SECOND(nn.Module):  # heter_encoders.py:52-81
     def forward(self, data_dict, modality_name):
         inp = data_dict[f'inputs_{modality_name}']
         voxel_features, voxel_coords, voxel_num_points = inp['voxel_features'], inp['voxel_coords'], inp['voxel_num_points']
-        batch_size = int(voxel_coords[:, 0].max()) + 1          # heter_encoders.py:70 (one host read, as in the reference)
+        # heter_encoders.py:70 (one host read, as in the reference); the same read brings the number of voxels inside the grid. The
+        # reference's dataloader emits no others; if some arrive they carry the key that sorts last, so the valid rows are a prefix.
+        # Dropping them here keeps all-zero phantom rows out of the batch statistics of conv_input / conv1 in train mode.
+        D, H, W = self.spconv_block.sparse_shape
+        c = voxel_coords
+        inside = (c >= 0).all(1) & (c[:, 1] < D) & (c[:, 2] < H) & (c[:, 3] < W)
+        top, n_inside = torch.stack([c[:, 0].max(), inside.sum()]).tolist()
+        batch_size, n_inside = int(top) + 1, int(n_inside)
         keys, perm = index_voxels(voxel_coords, batch_size, self.spconv_block.sparse_shape)
+        if n_inside < keys.shape[0]:
+            keys, perm = keys[:n_inside], perm[:n_inside]
         batch_dict = {'voxel_features': voxel_features, 'voxel_coords': voxel_coords, 'voxel_num_points': voxel_num_points,
                       'batch_size': batch_size, '_sorted_perm': perm}
         batch_dict = self.vfe(batch_dict)                       # rows come out in key order

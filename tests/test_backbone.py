@@ -241,8 +241,15 @@ def test_split_conv_kernels_hold_fp32_grade_accuracy_over_the_whole_input_range(
         ref = torch.nn.functional.conv2d(x.double(), conv.weight.double(), conv.bias.double(), stride=stride, padding=k // 2)
         mag = torch.nn.functional.conv2d(x.abs().double(), conv.weight.abs().double(), None, stride=stride, padding=k // 2) + conv.bias.abs().double().view(1, -1, 1, 1)
         for mode in (3, 1, 0):   # 3: the two-term split kernels (opt-in); 1, 0: exact fp32 (the default for these layers since round 3)
-            with _lib.mode(_lib.MODE_ARITH, mode):
+            with _lib.mode(_lib.MODE_ARITH, mode), _lib.kernel_log() as kl:
                 got = conv2d_hip(x.cuda(), conv.cuda(), None, relu=False).cpu().double()
+            # the kernel log: mode 3 ran the two-term split kernel of this shape and nothing else; modes 0 / 1 never run it
+            f16s = {name: cnt for name, cnt in kl.counts.items() if "_f16s_kernel" in name}
+            if mode == 3:
+                assert kl.counts == f16s and sum(f16s.values()) == 1, kl.counts
+                assert list(f16s)[0].startswith("conv3x3_f16s_kernel<%d>" % stride if k == 3 else "conv1x1_f16s_kernel<"), kl.counts
+            else:
+                assert not f16s, (mode, kl.counts)
             assert torch.isfinite(got).all(), (case, mode)
             worst = float(((got - ref).abs() / mag).max())
             assert worst <= 4e-6, (case, "split" if mode == 3 else "exact fp32", worst)
