@@ -39,6 +39,7 @@ _SIGNATURES = {
     "gencomm_klog_start": (_i, []),
     "gencomm_klog_stop": (_i, [C.c_char_p, _i]),
     "gencomm_clock_probe": (_i, [_p, _i, _p]),
+    "gencomm_quad_iou_fwd": (_i, [_p, _i, _p, _i, _p, _p]),
     "gencomm_unet_num_params": (_i, [_i, _i, _i, _i]),
     "gencomm_unet_param_info": (_i, [_i, _i, _i, _i, _i, C.c_char_p, _i, C.POINTER(_ll), C.POINTER(_ll)]),
     "gencomm_unet_raw_floats": (_ll, [_i, _i, _i, _i]),

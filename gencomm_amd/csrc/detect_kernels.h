@@ -58,7 +58,9 @@ __device__ __forceinline__ void det_box7(const float* __restrict__ reg, const fl
   b[6] = d[6] + ab[6];
 }
 
-struct BoxExtent { float xmin, xmax, ymin, ymax, zmin, zmax; };
+// finite: no projected corner is NaN or infinite (fminf / fmaxf skip a NaN, so the extents alone would let such a box pass, while the
+// reference's torch max / min propagate it and its comparisons then reject the box)
+struct BoxExtent { float xmin, xmax, ymin, ymax, zmin, zmax; bool finite; };
 
 // boxes_to_corners_3d (-> u, unprojected) + project_box3d (-> c); returns the extents of c
 __device__ __forceinline__ BoxExtent det_corners(const float (&b)[7], int hwl, const float* __restrict__ T, float (&u)[8][3],
@@ -67,7 +69,7 @@ __device__ __forceinline__ BoxExtent det_corners(const float (&b)[7], int hwl, c
   const float ex = hwl ? b[5] : b[3], ey = b[4], ez = hwl ? b[3] : b[5];
   const float cosa = cosf(b[6]), sina = sinf(b[6]);
   const float sx[8] = {1, 1, -1, -1, 1, 1, -1, -1}, sy[8] = {-1, 1, 1, -1, -1, 1, 1, -1}, sz[8] = {-1, -1, -1, -1, 1, 1, 1, 1};
-  BoxExtent e{INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
+  BoxExtent e{INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY, true};
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const float px = ex * (sx[k] / 2.f), py = ey * (sy[k] / 2.f), pz = ez * (sz[k] / 2.f);
@@ -83,6 +85,7 @@ __device__ __forceinline__ BoxExtent det_corners(const float (&b)[7], int hwl, c
     e.xmin = fminf(e.xmin, X); e.xmax = fmaxf(e.xmax, X);
     e.ymin = fminf(e.ymin, Y); e.ymax = fmaxf(e.ymax, Y);
     e.zmin = fminf(e.zmin, Z); e.zmax = fmaxf(e.zmax, Z);
+    e.finite = e.finite && X - X == 0.f && Y - Y == 0.f && Z - Z == 0.f;
   }
   return e;
 }
@@ -111,7 +114,7 @@ __device__ __forceinline__ bool det_decode_one(const DetArgs& a, int i, float (&
   // remove_large_pred_bbx: its "z extent" is the y extent again and is used as a truth value (non-zero)
   const bool size_ok = x_len <= 6.f && y_len <= 6.f && y_len != 0.f;
   const bool z_ok = e.zmin >= -3.f && e.zmax <= 1.f;
-  return size_ok && z_ok;
+  return e.finite && size_ok && z_ok;
 }
 
 __device__ __forceinline__ float det_score(const DetArgs& a, int i) {
@@ -257,7 +260,7 @@ __device__ __forceinline__ bool detmc_decode_one(const DetMcArgs& a, const DetMc
   // as in the single-class filter, the "z extent" is the y extent again, used as a truth value
   const bool size_ok = x_len <= 100.f && y_len <= 100.f && y_len != 0.f;
   const bool z_ok = e.zmin >= -100.f && e.zmax <= 100.f;
-  return size_ok && z_ok;
+  return e.finite && size_ok && z_ok;
 }
 
 // pass 1: class max + score filter -> score_tmp / label_tmp; candidates and filter violations per workgroup
@@ -391,9 +394,13 @@ __global__ __launch_bounds__(1024) void nms_sort_kernel(const float* __restrict_
   const int n = min(*n_dev, kNmsMaxN);
   int P = 1;
   while (P < n) P <<= 1;
-  // key: larger = earlier.  score > 0 so its bit pattern is monotone; ties -> larger index first
-  for (int i = threadIdx.x; i < P; i += 1024)
-    s_key[i] = i < n ? ((unsigned long long)__float_as_uint(scores[i]) << 32) | (unsigned)i : 0ull;
+  // key: larger = earlier.  The score's bit pattern with the sign bit set (score >= 0) or all bits inverted (score < 0) is
+  // monotone over every finite float (for positive scores it is the plain bit order); ties -> larger index first
+  for (int i = threadIdx.x; i < P; i += 1024) {
+    const unsigned u = i < n ? __float_as_uint(scores[i]) : 0u;
+    const unsigned key = u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+    s_key[i] = i < n ? ((unsigned long long)key << 32) | (unsigned)i : 0ull;
+  }
   __syncthreads();
   for (int k = 2; k <= P; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
@@ -451,6 +458,8 @@ __device__ __forceinline__ double quad_iou_d(const float* __restrict__ ca, const
   double ap = poly_area(p, 4), aq = poly_area(q, 4);
   if (ap < 0) { Pt t = p[0]; p[0] = p[3]; p[3] = t; t = p[1]; p[1] = p[2]; p[2] = t; ap = -ap; }
   if (aq < 0) { Pt t = q[0]; q[0] = q[3]; q[3] = t; t = q[1]; q[1] = q[2]; q[2] = t; aq = -aq; }
+  // a box without area shares no area with anything: exactly 0, where clipping against a rotated zero-width box left slivers of 1e-15
+  if (ap == 0.0 || aq == 0.0) return 0.0;
   Pt buf0[12], buf1[12];
   int n = 4;
   for (int k = 0; k < 4; ++k) buf0[k] = p[k];
@@ -462,6 +471,15 @@ __device__ __forceinline__ double quad_iou_d(const float* __restrict__ ca, const
   const double inter = fabs(poly_area(cur, n));
   const double uni = ap + aq - inter;
   return uni > 0 ? inter / uni : 0.0;
+}
+
+// diagnostic (gencomm_quad_iou_fwd): out[i][j] = the float64 IoU the mask kernel thresholds, one thread per pair
+__global__ __launch_bounds__(256) void quad_iou_kernel(const float* __restrict__ corners_a, const float* __restrict__ corners_b,
+                                                      double* __restrict__ out, int n_a, int n_b) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long long)n_a * n_b) return;
+  const int i = (int)(t / n_b), j = (int)(t - (long long)i * n_b);
+  out[t] = quad_iou_d(corners_a + (size_t)i * 24, corners_b + (size_t)j * 24);
 }
 
 // mask[i][w] bit b: candidate order[64 w + b] (ranked after i) overlaps candidate order[i] above the threshold

@@ -1183,6 +1183,17 @@ int gencomm_bbox_overlaps_fwd(const float* boxes, const float* query_boxes, floa
   return GC_OK;
 }
 
+int gencomm_quad_iou_fwd(const float* corners_a, int n_a, const float* corners_b, int n_b, double* out, void* stream) {
+  GC_CHECK_ARG(n_a >= 0 && n_b >= 0, "bad n_a/n_b");
+  if (n_a == 0 || n_b == 0) return GC_OK;
+  GC_CHECK_ARG(corners_a && corners_b && out, "null pointer");
+  const long long total = (long long)n_a * n_b;
+  GC_CHECK_ARG((total + 255) / 256 < (1LL << 31), "n_a*n_b too large");
+  quad_iou_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(corners_a, corners_b, out, n_a, n_b);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
 // ------------------------------------------------------------------------------------ fusion
 int gencomm_warp_attfuse_fwd(const float* x, const double* theta, const int* scene_off, float* out,
                              int B, int n, int C, int H, int W, void* stream) {

@@ -133,7 +133,8 @@ class VoxelPostprocessor:
         key = (str(device), H, W, A)
         if key not in self._cache:
             l = _lib.lib()
-            cap = min(H * W * A, l.gencomm_nms_max_candidates())
+            # every agent of a late-fusion call appends into these buffers: sized for the sort's limit, not for one agent's map
+            cap = l.gencomm_nms_max_candidates()
             top = 1000
             ws = max(_lib.check_size(l.gencomm_det_workspace_bytes(H, W, A), "gencomm_det_workspace_bytes"),
                      _lib.check_size(l.gencomm_nms_workspace_bytes(), "gencomm_nms_workspace_bytes"))

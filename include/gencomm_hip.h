@@ -142,6 +142,12 @@ int gencomm_klog_stop(char* buf, int cap);
  * workload (tools/diag/clock_under_load.py). */
 int gencomm_clock_probe(unsigned long long* out_dev, int spin_us, void* stream);
 
+/* Diagnostic: out[i][j] (double, [n_a][n_b], j fastest) = the convex-quadrilateral IoU that gencomm_nms_rotated_fwd compares with
+ * its threshold (before its rounding to float), of the BEV quadrilaterals (x, y of the first four corners) of corners_a[i] and
+ * corners_b[j]; corners_* are [n][8][3] float32 as the NMS takes them, either orientation. The same device function as the NMS
+ * (csrc/detect_kernels.h quad_iou_d), one thread per pair. n_a == 0 or n_b == 0 is a no-op. */
+int gencomm_quad_iou_fwd(const float* corners_a, int n_a, const float* corners_b, int n_b, double* out, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * UNet parameters.  The "raw" blob is the concatenation of the module's parameters in EXECUTION
  * order; enumerate it with gencomm_unet_param_info (name = the reference's state_dict key under
@@ -361,12 +367,14 @@ int gencomm_conv2d_act_res_fwd(const float* x, const float* prepared, const floa
  *   VoxelPostprocessor.post_process   opencood/data_utils/post_processor/voxel_postprocessor.py:1130-1244
  * det_decode: sigmoid(cls) > score_threshold, delta_to_boxes3d (:1351-1396), direction classifier fix (:1159-1175),
  *   boxes_to_corners_3d + project_box3d (box_utils.py:152-204, :278-316), remove_large_pred_bbx / remove_bbx_abnormal_z
- *   (box_utils.py:1062-1112); survivors are APPENDED in anchor order at position *count (device int, in/out -- zero it
+ *   (box_utils.py:1062-1112; a box with a NaN or infinite corner fails them, as torch's max / min propagate it there); survivors
+ *   are APPENDED in anchor order at position *count (device int, in/out -- zero it
  *   before the first agent, call once per agent for late fusion). Layouts: cls [A][H][W], reg [7A][H][W],
  *   dir [A*num_bins][H][W] or NULL, anchors [H][W][A][7] float32, transformation_matrix [16] float32 (device).
  *   corners [capacity][8][3], scores / anchor_index [capacity]; entries beyond capacity are dropped but still counted:
  *   the caller must compare *count with capacity.
- * nms_rotated: box_utils.nms_rotated (:915-960; scores sorted descending, exact ties by descending index; the `top`
+ * nms_rotated: box_utils.nms_rotated (:915-960; scores sorted descending, exact ties by descending index; any finite
+ *   float is a valid score -- negative ones and zero order as numbers do, -0.0 below +0.0; NaN is not; the `top`
  *   best kept, top <= 1024; IoU of the BEV quadrilaterals = first four corners, in float64, suppressed when
  *   (float)iou > iou_threshold), then -- when keep_range6 != NULL -- mask_boxes_outside_range_numpy (:384-421, all 8
  *   corners inside, bounds inclusive). *n_candidates is a DEVICE int (at most gencomm_nms_max_candidates() are
@@ -379,7 +387,7 @@ int gencomm_conv2d_act_res_fwd(const float* x, const float* prepared, const floa
  *   (no direction fix), boxes_to_corners_3d + project_box3d. Candidates in agent, then anchor order from slot 0: corners
  *   [capacity][8][3], unprojected [capacity][8][3] (may be NULL), scores, labels (1-based) [capacity]; *count (device) = all
  *   candidates (entries beyond capacity are dropped but counted), *violations (device) = candidates that
- *   remove_large_pred_bbx_v2xreal / remove_bbx_abnormal_z_v2xreal (box_utils.py:1115-1166) reject -- kept, not dropped:
+ *   remove_large_pred_bbx_v2xreal / remove_bbx_abnormal_z_v2xreal (box_utils.py:1115-1166) reject, a non-finite corner included -- kept, not dropped:
  *   the reference asserts there are none. Workspace: gencomm_det_mc_workspace_bytes (H, W: host arrays of n_agents).
  * det_mc_gather: after gencomm_nms_rotated_fwd on (corners, scores, count), score_labels[t] = {out_scores[t],
  *   labels[out_index[t]]} and out_unprojected[t] = unprojected[out_index[t]] (both NULL or neither) for t < *out_count. */

@@ -103,6 +103,46 @@ def test_hip_post_process_two_agents_and_empty():
 
 
 @pytest.mark.gpu
+def test_hip_post_process_late_fusion_exceeds_one_agents_anchor_count():
+    """Two agents on a 4 x 8 x 2 map, every anchor above the threshold, all 128 decoded boxes apart from each other: the candidates of the
+    call exceed H W A = 64 of one map. The candidate buffers hold the NMS's limit whatever the map size, so the call returns the oracle's
+    boxes (it used to hand the NMS a count above its buffers and raise afterwards)."""
+    from gencomm_amd.postprocess import VoxelPostprocessor
+    from oracle import detect_port as D
+    g = load_case("postproc")
+    params = json.loads(str(g["params"]))
+    dev = "cuda:0"
+    H, W, A = 4, 8, 2
+    anchors = np.zeros((H, W, A, 7))
+    anchors[..., 0] = (-28.0 + 8.0 * np.arange(W))[None, :, None]
+    anchors[..., 1] = (-16.0 + 8.0 * np.arange(H))[:, None, None] + np.array([0.0, 4.0])[None, None, :]   # the turned anchor 4 m aside
+    anchors[..., 2] = -1.0
+    anchors[..., 3:6] = [1.56, 1.6, 3.9]
+    anchors[..., 6] = np.array([0.0, np.pi / 2])[None, None, :]
+    anchors = torch.from_numpy(anchors)
+    r = np.random.RandomState(11)
+    T = [torch.eye(4), torch.eye(4)]
+    T[1][0, 3] = 4.0                                                   # the second agent's boxes between the first one's
+    cls = [torch.from_numpy(r.uniform(2.0, 5.0, (1, A, H, W)).astype(np.float32)) for _ in range(2)]
+    reg = [torch.zeros(1, 7 * A, H, W) for _ in range(2)]
+    pp = VoxelPostprocessor(params)
+    data = {k: {"transformation_matrix": T[i].to(dev), "anchor_box": anchors} for i, k in enumerate(("ego", "1"))}
+    out = {k: {"cls_preds": cls[i].to(dev), "reg_preds": reg[i].to(dev)} for i, k in enumerate(("ego", "1"))}
+    boxes, scores = pp.post_process(data, out)
+    cs, ss = [], []
+    for i in range(2):
+        c, s = D.post_process(cls[i], reg[i], None, anchors, T[i], {**params, "nms_thresh": 2.0, "gt_range": [-1e9] * 3 + [1e9] * 3})
+        cs.append(c); ss.append(s)
+    c_all, s_all = torch.cat(cs), torch.cat(ss)
+    assert c_all.shape[0] == 2 * H * W * A
+    k = D.nms_rotated(c_all.numpy(), s_all.numpy(), params["nms_thresh"])
+    m = D.mask_boxes_outside_range(c_all[k].numpy(), params["gt_range"])
+    assert len(k) == 2 * H * W * A and m.all()                         # nothing overlaps, nothing is out of range
+    np.testing.assert_allclose(scores.cpu().numpy(), s_all[k].numpy(), rtol=0, atol=2e-7)
+    np.testing.assert_allclose(boxes.cpu().numpy(), c_all[k].numpy(), rtol=0, atol=3e-5)
+
+
+@pytest.mark.gpu
 def test_hip_bbox_overlaps_bit_exact():
     from gencomm_amd.postprocess import bbox_overlaps
     g = load_case("postproc")
