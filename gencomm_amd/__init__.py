@@ -8,7 +8,7 @@ Public surface mirrors the reference's plugin API:
     AttFusion(feature_dims)            opencood/models/fuse_modules/fusion_in_one.py:126
     MaxFusion()                        opencood/models/fuse_modules/fusion_in_one.py:87 (fusion_method: max)
     Who2comFusion(feature_dims)        opencood/models/fuse_modules/fusion_in_one.py:521 (fusion_method: who2com)
-    CoBEVT(args)                       opencood/models/fuse_modules/fusion_in_one.py:409 (fusion_method: cobevt; inference)
+    CoBEVT(args)                       opencood/models/fuse_modules/fusion_in_one.py:409 (fusion_method: cobevt; trainable=True trains)
     V2VNetFusion(args)                 opencood/models/fuse_modules/fusion_in_one.py:238 (the v2vnet block; a component; trainable=True trains)
     regroup, normalize_pairwise_tfm    fusion_in_one.py:48, opencood/utils/transformation_utils.py:68
     MessageExtractorv2(in_ch, out_ch)  opencood/models/gencomm_modules/message_extractor_v2.py:109

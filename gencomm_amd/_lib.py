@@ -115,6 +115,8 @@ _SIGNATURES = {
     "gencomm_hgt_attn_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "gencomm_win_attn_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "gencomm_swap_attn_fwd": (_i, [_p, _p, _p, _p] + [_i] * 8 + [_p]),
+    "gencomm_swap_attn_train_fwd": (_i, [_p] * 5 + [_i] * 8 + [_p]),
+    "gencomm_swap_attn_bwd": (_i, [_p] * 8 + [_i] * 8 + [_p]),
     "gencomm_agent_mean_fwd": (_i, [_p, _p, _i, _i, _ll, _p]),
     "gencomm_v2v_warp_pairs_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "gencomm_v2v_aggregate_fwd": (_i, [_p] * 7 + [_i] * 6 + [_p]),

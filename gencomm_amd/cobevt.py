@@ -16,8 +16,12 @@ The ``torch.nn`` classes below are parameter containers; ``forward`` runs on the
 Padded agents ARE materialised, unlike in V2XViTFusion: their rows are zero only before the first residual, they are queries of every
 attention, and the head averages over all ``agent_size`` rows (swap_fusion_modules.py:275).
 
-Inference only: dropout is the identity in ``eval()``; a call with gradients enabled into a module that has a parameter or an input
-requiring grad, and ``train()`` mode with ``drop_out > 0``, raise ``NotImplementedError`` (the attention backward is a follow-up).
+``CoBEVT(args)`` infers only: dropout is the identity in ``eval()``; a call with gradients enabled into a module that has a parameter
+or an input requiring grad, and ``train()`` mode with ``drop_out > 0``, raise ``NotImplementedError``. ``CoBEVT(args, trainable=True)``
+(what the model shells construct; the precedent is ``V2VNetFusion(args, trainable=True)``) sends those calls through
+``cobevt_bwd.CoBEVTFunction``: the same kernel calls with the attention through ``gencomm_swap_attn_train_fwd`` (bit-identical output
+while dropout is inactive), a tape of what the backward reads, the dropout masks of ``train()`` mode, and the HIP backward around
+``gencomm_swap_attn_bwd``. ``trainable`` adds no parameter or buffer: the ``state_dict`` is the same.
 """
 from __future__ import annotations
 
@@ -74,8 +78,9 @@ class SwapFusionBlockMask(nn.Module):  # swap_fusion_modules.py:131-163
 
 # ----------------------------------------------------------------------------------------- the module
 class CoBEVT(nn.Module):
-    def __init__(self, args):
+    def __init__(self, args, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.depth = args["depth"]
         input_dim, mlp_dim, dim_head = args["input_dim"], args["mlp_dim"], args["dim_head"]
         self.agent_size, self.window_size, self.drop_out = args["agent_size"], args["window_size"], float(args["drop_out"])
@@ -107,37 +112,69 @@ class CoBEVT(nn.Module):
             raise ValueError(f"CoBEVT: input has {C} channels, the module was built with input_dim {self.mlp_head[2].normalized_shape[0]}")
         if H % ws or W % ws:
             raise ValueError(f"CoBEVT: H and W must be multiples of window_size ({ws}), got {H}x{W}")
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        dropout = self.training and self.drop_out > 0
+        if self.trainable and (grad or dropout):
+            require_gpu(x, "CoBEVT.forward")
+            from .cobevt_bwd import CoBEVTFunction
+            return CoBEVTFunction.apply(self, x, lens, affine_matrix, *self.parameters())
+        if grad:
             raise NotImplementedError("cobevt training is not implemented (the swap-attention backward is missing): call under torch.no_grad() "
                                       "or freeze the module")
-        if self.training and self.drop_out > 0:
+        if dropout:
             raise NotImplementedError(f"cobevt training is not implemented: train() mode with drop_out {self.drop_out} > 0 needs the dropout "
                                       "masks; call eval()")
         require_gpu(x, "CoBEVT.forward")
         with torch.no_grad():
             return self._forward_hip(f32c(x), lens, affine_matrix)
 
-    def _attention(self, key, pre: PreNormResidual, h, nvalid, B, grid_mode):
-        """h + to_out(swap attention(to_qkv(LN(h)))) over the padded batch h [B L, C, H, W]."""
+    def _attention(self, key, pre: PreNormResidual, h, nvalid, B, grid_mode, tape=None, masks=None):
+        """h + to_out(swap attention(to_qkv(LN(h)))) over the padded batch h [B L, C, H, W]. With a `tape` (training) the attention goes
+        through gencomm_swap_attn_train_fwd (the same `out`, plus lse) and the tape receives what the backward reads."""
         att, dev, cache = pre.fn, h.device, self._linears
         n, C, H, W = h.shape
         hn = T.ln_fwd(h, pre.norm.weight, pre.norm.bias, pre.norm.eps, False)
         qkv = _linear(hn, cache.get((key, "qkv"), [att.to_qkv.weight], lambda: (att.to_qkv.weight, None), dev))
         out = torch.empty_like(h)
         table = f32c(att.relative_position_bias_table.weight.detach())
-        _lib.check(_lib.lib().gencomm_swap_attn_fwd(ptr(qkv), ptr(table), ptr(nvalid), ptr(out), B, n // B, att.heads, att.dim_head,
-                                                    self.window_size, H, W, int(grid_mode), stream_ptr(dev)), "gencomm_swap_attn_fwd")
+        dims = (B, n // B, att.heads, att.dim_head, self.window_size, H, W, int(grid_mode), stream_ptr(dev))
         o = att.to_out[0]
-        return _linear(out, cache.get((key, "out"), [o.weight], lambda: (o.weight, None), dev), 0, h)
+        entry = cache.get((key, "out"), [o.weight], lambda: (o.weight, None), dev)
+        if tape is None:
+            _lib.check(_lib.lib().gencomm_swap_attn_fwd(ptr(qkv), ptr(table), ptr(nvalid), ptr(out), *dims), "gencomm_swap_attn_fwd")
+            return _linear(out, entry, 0, h)
+        lse = torch.empty(n, att.heads, H, W, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().gencomm_swap_attn_train_fwd(ptr(qkv), ptr(table), ptr(nvalid), ptr(out), ptr(lse), *dims), "gencomm_swap_attn_train_fwd")
+        p = float(att.to_out[1].p)
+        if masks.active and p > 0:
+            y, m = masks.apply(_linear(out, entry), p)
+            y = y + h
+        else:
+            y, m = _linear(out, entry, 0, h), None
+        tape.append(("att", pre, int(grid_mode), h, qkv, out, lse, table, m))
+        return y
 
-    def _feed_forward(self, key, pre: PreNormResidual, h):
+    def _feed_forward(self, key, pre: PreNormResidual, h, tape=None, masks=None):
         dev, cache = h.device, self._linears
         hn = T.ln_fwd(h, pre.norm.weight, pre.norm.bias, pre.norm.eps, False)
         l0, l3 = pre.fn.net[0], pre.fn.net[3]
         mid = _linear(hn, cache.get((key, "ff0"), [l0.weight, l0.bias], lambda: (l0.weight, l0.bias), dev), 2)        # Linear + GELU
-        return _linear(mid, cache.get((key, "ff3"), [l3.weight, l3.bias], lambda: (l3.weight, l3.bias), dev), 0, h)   # Linear + residual
+        e3 = cache.get((key, "ff3"), [l3.weight, l3.bias], lambda: (l3.weight, l3.bias), dev)
+        if tape is None:
+            return _linear(mid, e3, 0, h)                                                                             # Linear + residual
+        p = float(pre.fn.net[2].p)
+        if masks.active and p > 0:
+            mid, m_mid = masks.apply(mid, p)
+            y, m_out = masks.apply(_linear(mid, e3), p)
+            y = y + h
+        else:
+            y, m_mid, m_out = _linear(mid, e3, 0, h), None, None
+        tape.append(("ff", pre, h, mid, m_mid, m_out))
+        return y
 
-    def _forward_hip(self, x, lens, affine_matrix):
+    def _forward_hip(self, x, lens, affine_matrix, tape=None, masks=None):
+        """`tape` (a list) and `masks` (v2xvit_bwd._Masks): the training forward of cobevt_bwd.CoBEVTFunction. The kernel calls are the
+        same (the attention through the train entry); with dropout active the epilogue-fused residuals become separate additions."""
         n, C, H, W = x.shape
         B, L = affine_matrix.shape[:2]
         l, dev = _lib.lib(), x.device
@@ -151,12 +188,14 @@ class CoBEVT(nn.Module):
             off += k
         nvalid = dev_ints(lens, dev)
         for i, blk in enumerate(self.layers):
-            h = self._attention((i, "window"), blk.window_attention, h, nvalid, B, 0)
-            h = self._feed_forward((i, "window"), blk.window_ffd, h)
-            h = self._attention((i, "grid"), blk.grid_attention, h, nvalid, B, 1)
-            h = self._feed_forward((i, "grid"), blk.grid_ffd, h)
+            h = self._attention((i, "window"), blk.window_attention, h, nvalid, B, 0, tape, masks)
+            h = self._feed_forward((i, "window"), blk.window_ffd, h, tape, masks)
+            h = self._attention((i, "grid"), blk.grid_attention, h, nvalid, B, 1, tape, masks)
+            h = self._feed_forward((i, "grid"), blk.grid_ffd, h, tape, masks)
         mean = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
         _lib.check(l.gencomm_agent_mean_fwd(ptr(h), ptr(mean), B, L, C * H * W, st), "gencomm_agent_mean_fwd")
         norm, lin = self.mlp_head[2], self.mlp_head[3]
         hn = T.ln_fwd(mean, norm.weight, norm.bias, norm.eps, False)
+        if tape is not None:
+            tape.append(("head", mean, hn, theta, nvalid))
         return _linear(hn, self._linears.get("head", [lin.weight, lin.bias], lambda: (lin.weight, lin.bias), dev))

@@ -11,6 +11,7 @@
 #include "loss_kernels.h"
 #include "lss_kernels.h"
 #include "sparse_kernels.h"
+#include "swap_attn_bwd_kernels.h"
 #include "swap_attn_kernels.h"
 #include "target_kernels.h"
 #include "v2v_kernels.h"
@@ -173,9 +174,7 @@ int gencomm_win_attn_fwd(const float* qkv, const float* pos_embedding, float* ou
 }
 
 // ---- CoBEVT (swap_attn_kernels.h) ---------------------------------------------------------------------------------------
-int gencomm_swap_attn_fwd(const float* qkv, const float* bias_table, const int* num_agents, float* out, int B, int L, int heads, int dim_head,
-                          int window, int H, int W, int grid_mode, void* stream) {
-  GC_CHECK_ARG(qkv && bias_table && num_agents && out, "null pointer");
+static int swap_attn_check(int B, int L, int heads, int dim_head, int window, int H, int W, int grid_mode) {
   GC_CHECK_ARG(B >= 1 && B <= 65535 && heads >= 1 && heads <= 65535, "swap attention: 1..65535 scenes and heads");
   GC_CHECK_ARG(L >= 1 && L <= kSwapMaxAgents, "swap attention: agent_size (L) must be 1..8");
   GC_CHECK_ARG(grid_mode == 0 || grid_mode == 1, "swap attention: grid_mode must be 0 (window partition) or 1 (grid partition)");
@@ -183,14 +182,38 @@ int gencomm_swap_attn_fwd(const float* qkv, const float* bias_table, const int* 
   GC_CHECK_ARG(dim_head == 16 || dim_head == 32 || dim_head == 64, "swap attention: dim_head must be 16, 32 or 64");
   GC_CHECK_ARG(H >= window && W >= window && H % window == 0 && W % window == 0, "swap attention: H and W must be multiples of window_size");
   GC_CHECK_ARG((long long)H * W * 3 * heads * dim_head < (1LL << 31), "swap attention: one agent's qkv map must stay below 2^31 elements");
-  SwapArgs a{qkv, bias_table, num_agents, out, L, heads, H, W, grid_mode, 0, 0, 1.0f / sqrtf((float)dim_head)};
+  return GC_OK;
+}
+
+int gencomm_swap_attn_fwd(const float* qkv, const float* bias_table, const int* num_agents, float* out, int B, int L, int heads, int dim_head,
+                          int window, int H, int W, int grid_mode, void* stream) {
+  GC_CHECK_ARG(qkv && bias_table && num_agents && out, "null pointer");
+  if (int rc = swap_attn_check(B, L, heads, dim_head, window, H, W, grid_mode)) return rc;
+  SwapArgs a{qkv, bias_table, num_agents, out, L, heads, H, W, grid_mode, 0, 0, 1.0f / sqrtf((float)dim_head), nullptr};
+  return swap_attn_dispatch<false>(a, B, dim_head, window, (hipStream_t)stream);
+}
+
+int gencomm_swap_attn_train_fwd(const float* qkv, const float* bias_table, const int* num_agents, float* out, float* lse, int B, int L, int heads,
+                                int dim_head, int window, int H, int W, int grid_mode, void* stream) {
+  GC_CHECK_ARG(qkv && bias_table && num_agents && out && lse, "null pointer");
+  if (int rc = swap_attn_check(B, L, heads, dim_head, window, H, W, grid_mode)) return rc;
+  SwapArgs a{qkv, bias_table, num_agents, out, L, heads, H, W, grid_mode, 0, 0, 1.0f / sqrtf((float)dim_head), lse};
+  return swap_attn_dispatch<true>(a, B, dim_head, window, (hipStream_t)stream);
+}
+
+int gencomm_swap_attn_bwd(const float* qkv, const float* bias_table, const int* num_agents, const float* out, const float* lse, const float* dout,
+                          float* dqkv, float* dtable, int B, int L, int heads, int dim_head, int window, int H, int W, int grid_mode,
+                          void* stream) {
+  GC_CHECK_ARG(qkv && bias_table && num_agents && out && lse && dout && dqkv && dtable, "null pointer");
+  if (int rc = swap_attn_check(B, L, heads, dim_head, window, H, W, grid_mode)) return rc;
+  SwapBwdArgs a{qkv, bias_table, num_agents, out, lse, dout, dqkv, dtable, L, heads, H, W, grid_mode, 0, 0, 0, 1.0f / sqrtf((float)dim_head)};
   hipStream_t st = (hipStream_t)stream;
-  if (window == 4 && dim_head == 16) return swap_attn_launch<16, 4>(a, B, st);
-  if (window == 4 && dim_head == 32) return swap_attn_launch<32, 4>(a, B, st);
-  if (window == 4 && dim_head == 64) return swap_attn_launch<64, 4>(a, B, st);
-  if (window == 8 && dim_head == 16) return swap_attn_launch<16, 8>(a, B, st);
-  if (window == 8 && dim_head == 32) return swap_attn_launch<32, 8>(a, B, st);
-  return swap_attn_launch<64, 8>(a, B, st);
+  if (window == 4 && dim_head == 16) return swap_attn_bwd_launch<16, 4>(a, B, st);
+  if (window == 4 && dim_head == 32) return swap_attn_bwd_launch<32, 4>(a, B, st);
+  if (window == 4 && dim_head == 64) return swap_attn_bwd_launch<64, 4>(a, B, st);
+  if (window == 8 && dim_head == 16) return swap_attn_bwd_launch<16, 8>(a, B, st);
+  if (window == 8 && dim_head == 32) return swap_attn_bwd_launch<32, 8>(a, B, st);
+  return swap_attn_bwd_launch<64, 8>(a, B, st);
 }
 
 int gencomm_agent_mean_fwd(const float* x, float* out, int B, int L, long long count, void* stream) {

@@ -23,6 +23,8 @@
 // group, so the key loop ends at the last VALID agent: masked agents cost nothing at ws 8 and at most part of one tile at ws 4.
 // A workgroup = up to 8 query blocks of one (group, head, scene); a group of more than 256 tokens is split evenly over several
 // workgroups, each staging the group's keys for itself.
+// swap_attn_kernel<DH, WS, true> (gencomm_swap_attn_train_fwd) is the same body with one more store per query, lse = running max +
+// log(running denominator), which swap_attn_bwd_kernels.h turns back into the probabilities; `out` is computed by the same instructions.
 #pragma once
 #include "common.h"
 
@@ -38,11 +40,12 @@ struct SwapArgs {
   int L, heads, H, W, grid_mode;
   int nqb, wpc;         // query blocks of 32 per group; query blocks (= waves) per workgroup
   float scale;
+  float* lse;           // [B * L][heads][H][W], written by the TRAIN instantiation only: running max + log(running denominator)
 };
 
 using f32x16s = __attribute__((ext_vector_type(16))) float;
 
-template <int DH, int WS>
+template <int DH, int WS, bool TRAIN = false>
 __global__ __launch_bounds__(512) void swap_attn_kernel(const SwapArgs a) {
   constexpr int T1 = WS * WS, KT = 64, LDK = DH + 1, DV = DH < 32 ? 32 : DH, LDV = DV + 1, PW = 2 * WS - 1, PW2 = PW * PW;
   constexpr int CH = DH < 32 ? DH : 32;   // channels a fill thread has in flight
@@ -159,16 +162,17 @@ __global__ __launch_bounds__(512) void swap_attn_kernel(const SwapArgs a) {
       const int ch = 32 * db + 8 * (r >> 2) + 4 * h + (r & 3);
       if (DH >= 32 || (r >> 2) < DH / 8) op[(size_t)ch * HW] = o[db][r] * rden;
     }
+  if (TRAIN && h == 0) a.lse[((size_t)(b * L + ql) * a.heads + m) * HW + qpix] = mrun + logf(den);
 }
 
-inline void swap_attn_klog(int dh, int ws) {
+inline void swap_attn_klog(int dh, int ws, const char* kernel = "swap_attn_kernel", const char* tail = "") {
   if (!klog_armed()) return;
   char name[64];
-  snprintf(name, sizeof name, "swap_attn_kernel<%d,%d>", dh, ws);
+  snprintf(name, sizeof name, "%s<%d,%d%s>", kernel, dh, ws, tail);
   klog_note(name);
 }
 
-template <int DH, int WS>
+template <int DH, int WS, bool TRAIN = false>
 inline int swap_attn_launch(SwapArgs a, int B, hipStream_t st) {
   constexpr int DV = DH < 32 ? 32 : DH, PW = 2 * WS - 1;
   a.nqb = (a.L * WS * WS + 31) / 32;
@@ -176,13 +180,24 @@ inline int swap_attn_launch(SwapArgs a, int B, hipStream_t st) {
   a.wpc = (a.nqb + split - 1) / split;
   const int nchunk = (a.nqb + a.wpc - 1) / a.wpc;
   const size_t shm = ((size_t)64 * (DH + 1) + 64 * (DV + 1) + (2 * a.L - 1) * PW * PW) * sizeof(float);
-  if (shm > 48 * 1024) GC_HIP(hipFuncSetAttribute((const void*)swap_attn_kernel<DH, WS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  if (shm > 48 * 1024)
+    GC_HIP(hipFuncSetAttribute((const void*)swap_attn_kernel<DH, WS, TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   const long long groups = (long long)(a.H / WS) * (a.W / WS) * nchunk;
   GC_CHECK_ARG(groups < (1LL << 31), "swap attention: too many groups for one launch");
-  swap_attn_klog(DH, WS);
-  swap_attn_kernel<DH, WS><<<dim3((unsigned)groups, a.heads, B), 64 * a.wpc, shm, st>>>(a);
+  swap_attn_klog(DH, WS, "swap_attn_kernel", TRAIN ? ",train" : "");
+  swap_attn_kernel<DH, WS, TRAIN><<<dim3((unsigned)groups, a.heads, B), 64 * a.wpc, shm, st>>>(a);
   GC_HIP(hipGetLastError());
   return GC_OK;
+}
+
+template <bool TRAIN>
+inline int swap_attn_dispatch(const SwapArgs& a, int B, int dim_head, int window, hipStream_t st) {
+  if (window == 4 && dim_head == 16) return swap_attn_launch<16, 4, TRAIN>(a, B, st);
+  if (window == 4 && dim_head == 32) return swap_attn_launch<32, 4, TRAIN>(a, B, st);
+  if (window == 4 && dim_head == 64) return swap_attn_launch<64, 4, TRAIN>(a, B, st);
+  if (window == 8 && dim_head == 16) return swap_attn_launch<16, 8, TRAIN>(a, B, st);
+  if (window == 8 && dim_head == 32) return swap_attn_launch<32, 8, TRAIN>(a, B, st);
+  return swap_attn_launch<64, 8, TRAIN>(a, B, st);
 }
 
 // out [B][count] = mean over the L rows of x [B][L][count], summed in agent order (count = C * H * W)

@@ -128,7 +128,7 @@ class HeterModelBaselineWGenComm(nn.Module):
             self.fusion_net = Where2commFusion(args["where2comm"])  # stage1.py:126-127
         elif method == "cobevt":
             from .cobevt import CoBEVT
-            self.fusion_net = CoBEVT(args["cobevt"])  # stage1.py:124-125
+            self.fusion_net = CoBEVT(args["cobevt"], trainable=True)  # stage1.py:124-125
         elif method == "who2com":
             from .who2com import Who2comFusion
             self.fusion_net = Who2comFusion(args["who2com"])  # stage1.py:127-128 (the block itself is the channel count)

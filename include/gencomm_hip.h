@@ -599,10 +599,29 @@ int gencomm_win_attn_bwd(const float* qkv, const float* pos_embedding, const flo
  *                            queries of all L agents are computed; values outside 1 .. L are clamped.  window 4 or 8, dim_head 16, 32
  *                            or 64, L <= 8, H and W multiples of window: anything else is an argument error
  *   gencomm_agent_mean_fwd   out [B][count] = mean over the L rows of x [B][L][count]
+ * Training (gencomm_amd/cobevt_bwd.py):
+ *   gencomm_swap_attn_train_fwd  gencomm_swap_attn_fwd plus lse [B L][heads][H][W]: per query the running max plus the log of the
+ *                            running softmax denominator.  Same kernel template with one more store: `out` is bit-identical to
+ *                            gencomm_swap_attn_fwd's on the same inputs
+ *   gencomm_swap_attn_bwd    the adjoint, from the forward's inputs, `out` and `lse` and the output gradient dout [B L][heads dim_head]
+ *                            [H][W].  With P_ij = exp(s_ij - lse_i): D_i = sum_d dO_id O_id, dS_ij = P_ij (dO_i . v_j - D_i),
+ *                            dQ_i = scale sum_j dS_ij k_j, dK_j = scale sum_i dS_ij q_i, dV_j = sum_i P_ij dO_i.
+ *                            dqkv [B L][3 heads dim_head][H][W] is OVERWRITTEN: every element is stored exactly once, nothing is read
+ *                            from it and no atomics touch it; the k and v rows of masked agents (l >= num_agents[b]) get exact zeros,
+ *                            the queries of all L agents take part.  dtable [(2 L - 1)(2 window - 1)^2][heads] is ACCUMULATED
+ *                            (dtable[rel(i, j)][head] += dS_ij over every group and scene): the caller zeroes it.  The sum goes
+ *                            through a per-workgroup table in LDS and then global float atomics, so its order is NOT fixed: dtable
+ *                            may differ in the last bits between two runs, dqkv may not.  Two launches (a query pass and a key pass,
+ *                            both recomputing the scores on the fp32 matrix cores), no scratch.  Same domain as the forward
  * -------------------------------------------------------------------------------------------- */
 int gencomm_swap_attn_fwd(const float* qkv, const float* bias_table, const int* num_agents, float* out, int B, int L, int heads, int dim_head,
                           int window, int H, int W, int grid_mode, void* stream);
 int gencomm_agent_mean_fwd(const float* x, float* out, int B, int L, long long count, void* stream);
+int gencomm_swap_attn_train_fwd(const float* qkv, const float* bias_table, const int* num_agents, float* out, float* lse, int B, int L, int heads,
+                                int dim_head, int window, int H, int W, int grid_mode, void* stream);
+int gencomm_swap_attn_bwd(const float* qkv, const float* bias_table, const int* num_agents, const float* out, const float* lse, const float* dout,
+                          float* dqkv, float* dtable, int B, int L, int heads, int dim_head, int window, int H, int W, int grid_mode,
+                          void* stream);
 /* V2VNet fusion building blocks (opencood/models/fuse_modules/fusion_in_one.py:238-353, sub_modules/convgru.py); gencomm_amd/v2vnet.py is
  * the module with the reference's state_dict keys. The convolutions between them run through gencomm_conv2d_fwd.
  *   gencomm_v2v_warp_pairs_fwd  out[p] = warp_affine_simple(x[src_row[p]], theta[p]) for P (target, source) pairs; x [rows][C][H][W] is
