@@ -14,10 +14,12 @@ Public surface mirrors the reference's plugin API:
     MessageExtractorv2(in_ch, out_ch)  opencood/models/gencomm_modules/message_extractor_v2.py:109
     LiftSplatShoot(args)               opencood/models/heter_encoders.py:83 (camera_encoder: Resnet101; trainable=True trains it)
     PointPillarDepthLoss(args)         opencood/loss/point_pillar_depth_loss.py:11 (loss.core_method: point_pillar_depth_loss)
+    UMGMQuantizer(channel, m, k, ...)  opencood/models/sub_modules/codebook.py:280 (the CodeFilling codebook codec; a component, inference)
 
 All compute runs in hand-written HIP kernels behind the C ABI of ``include/gencomm_hip.h``.
 """
 from .cobevt import CoBEVT
+from .codebook import UMGMQuantizer
 from .cond_diff import GenComm
 from .enhancer import Enhancer
 from .fusion import AttFusion, MaxFusion, normalize_pairwise_tfm, regroup
@@ -41,5 +43,5 @@ def set_denoise_dtype(dtype) -> None:
     _lib.check(_lib.lib().gencomm_set_mode(_lib.MODE_ARITH, value), "gencomm_set_mode")
 
 
-__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "MaxFusion", "Who2comFusion", "CoBEVT", "V2VNetFusion", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "regroup", "normalize_pairwise_tfm",
+__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "MaxFusion", "Who2comFusion", "CoBEVT", "V2VNetFusion", "UMGMQuantizer", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "regroup", "normalize_pairwise_tfm",
            "set_denoise_dtype"]

@@ -126,6 +126,12 @@ _SIGNATURES = {
     "gencomm_v2v_aggregate_bwd": (_i, [_p] * 7 + [_i] * 6 + [_p]),
     "gencomm_v2v_warp_pairs_bwd_scratch_floats": (_ll, [_i]),
     "gencomm_v2v_warp_pairs_bwd": (_i, [_p] * 7 + [_i] * 6 + [_p]),
+    "gencomm_umgm_param_floats": (_ll, [_i, _i, C.POINTER(_i), _i]),
+    "gencomm_umgm_workspace_bytes": (_ll, [_ll, _i]),
+    "gencomm_umgm_fwd": (_i, [_p, _p, _p, _p, C.c_ulonglong, _i, _p, _p, _p, _p, _p, _ll, _i, _i, _i, C.POINTER(_i), _i, _p, _ll, _p]),
+    "gencomm_umgm_encode_fwd": (_i, [_p, _p, _p, _ll, _i, _i, _i, C.POINTER(_i), _i, _p]),
+    "gencomm_umgm_decode_fwd": (_i, [_p, _p, _p, _ll, _i, _i, _i, C.POINTER(_i), _i, _p]),
+    "gencomm_umgm_noise_fwd": (_i, [_p, C.c_ulonglong, _ll, _i, C.POINTER(_i), _i, _p]),
     "gencomm_iou3d_pairwise_fwd": (_i, [_p, _i, _p, _i, _i, _p, _p]),
     "gencomm_iou3d_max_boxes": (_i, []),
     "gencomm_iou3d_nms_workspace_bytes": (_ll, [_i]),

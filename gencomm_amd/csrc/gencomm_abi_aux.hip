@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "codebook_kernels.h"
 #include "iou3d_kernels.h"
 #include "loss_kernels.h"
 #include "lss_kernels.h"
@@ -923,5 +924,86 @@ int gencomm_depth_focal_loss(const float* depth_logit, const long long* target, 
   return GC_OK;
 }
 
-}  // extern "C"
+// ---- CodeFilling codebook codec (codebook_kernels.h)
+long long gencomm_umgm_param_floats(int C, int m, const int* k, int levels) {
+  if (umgm_check_shape(C, m, k, levels) != GC_OK) return -1;
+  long long total = 0;
+  for (int l = 0; l < levels; ++l) total += umgm_level_floats(C, k[l]);
+  return total;
+}
 
+long long gencomm_umgm_workspace_bytes(long long n, int C) {
+  if (n < 1 || !(C == 64 || C == 128 || C == 256)) {
+    fail(GC_ERR_ARG, "umgm workspace: n must be at least 1 and channel 64, 128 or 256");
+    return -1;
+  }
+  return (long long)((n + kUmgmRows - 1) / kUmgmRows) * (long long)sizeof(float);
+}
+
+static int umgm_rows(long long n, int HW, long long* rows) {
+  GC_CHECK_ARG(n >= 1, "umgm: n must be at least 1");
+  GC_CHECK_ARG(HW >= 0 && HW < (1 << 30), "umgm: HW must be 0 (rows [n][C]) or the pixels of one NCHW map");
+  *rows = HW > 0 ? n * HW : n;   // NCHW: n counts agents
+  return GC_OK;
+}
+
+int gencomm_umgm_fwd(const float* params, const float* x, const unsigned char* keep, const float* uniforms, unsigned long long seed, int noise,
+                     float* restored, long long* codes, long long* sampled, float* logits, float* code_loss, long long n, int HW, int C, int m,
+                     const int* k, int levels, void* workspace, long long workspace_bytes, void* stream) {
+  if (int rc = umgm_check_shape(C, m, k, levels)) return rc;
+  GC_CHECK_ARG(params && x && restored && codes && code_loss, "umgm forward: null pointer");
+  GC_CHECK_ARG(noise >= UMGM_NOISE_NONE && noise <= UMGM_NOISE_PHILOX, "umgm forward: noise must be 0 (none), 1 (uniforms) or 2 (Philox)");
+  GC_CHECK_ARG(noise != UMGM_NOISE_UNIFORMS || uniforms, "umgm forward: null pointer (uniforms with noise 1)");
+  GC_CHECK_ARG(keep == nullptr || HW > 0, "umgm forward: keep needs the NCHW entry (HW > 0)");
+  GC_CHECK_ARG(((((uintptr_t)params | (uintptr_t)x | (uintptr_t)restored)) & 15) == 0, "umgm forward: params, x and restored must be 16-byte aligned");
+  long long rows = 0;
+  if (int rc = umgm_rows(n, HW, &rows)) return rc;
+  const long long need = gencomm_umgm_workspace_bytes(rows, C);
+  if (workspace == nullptr || workspace_bytes < need) return fail(GC_ERR_WORKSPACE, "umgm forward: workspace too small (gencomm_umgm_workspace_bytes)");
+  UmgmArgs a{};
+  a.params = params; a.x = x; a.keep = keep; a.uniforms = uniforms; a.out = restored; a.codes = codes; a.sampled = sampled; a.logits = logits;
+  a.partials = (float*)workspace; a.n = rows; a.seed = seed; a.HW = HW; a.m = m; a.L = levels; a.task = UMGM_FORWARD; a.noise = noise;
+  return umgm_launch(a, C, k, code_loss, (hipStream_t)stream);
+}
+
+int gencomm_umgm_encode_fwd(const float* params, const float* x, long long* codes, long long n, int HW, int C, int m, const int* k, int levels,
+                            void* stream) {
+  if (int rc = umgm_check_shape(C, m, k, levels)) return rc;
+  GC_CHECK_ARG(params && x && codes, "umgm encode: null pointer");
+  GC_CHECK_ARG((((uintptr_t)params | (uintptr_t)x) & 15) == 0, "umgm encode: params and x must be 16-byte aligned");
+  long long rows = 0;
+  if (int rc = umgm_rows(n, HW, &rows)) return rc;
+  UmgmArgs a{};
+  a.params = params; a.x = x; a.codes = codes; a.n = rows; a.HW = HW; a.m = m; a.L = levels; a.task = UMGM_ENCODE; a.noise = UMGM_NOISE_NONE;
+  return umgm_launch(a, C, k, nullptr, (hipStream_t)stream);
+}
+
+int gencomm_umgm_decode_fwd(const float* params, const long long* codes, float* restored, long long n, int HW, int C, int m, const int* k, int levels,
+                            void* stream) {
+  if (int rc = umgm_check_shape(C, m, k, levels)) return rc;
+  GC_CHECK_ARG(params && codes && restored, "umgm decode: null pointer");
+  GC_CHECK_ARG((((uintptr_t)params | (uintptr_t)restored) & 15) == 0, "umgm decode: params and restored must be 16-byte aligned");
+  long long rows = 0;
+  if (int rc = umgm_rows(n, HW, &rows)) return rc;
+  UmgmArgs a{};
+  a.params = params; a.codes = const_cast<long long*>(codes); a.out = restored; a.n = rows; a.HW = HW; a.m = m; a.L = levels; a.task = UMGM_DECODE;
+  a.noise = UMGM_NOISE_NONE;
+  return umgm_launch(a, C, k, nullptr, (hipStream_t)stream);
+}
+
+int gencomm_umgm_noise_fwd(float* out, unsigned long long seed, long long n, int m, const int* k, int levels, void* stream) {
+  if (int rc = umgm_check_shape(64, m, k, levels)) return rc;
+  GC_CHECK_ARG(out && ((uintptr_t)out & 15) == 0, "umgm noise: out must be a 16-byte aligned pointer");
+  GC_CHECK_ARG(n >= 1, "umgm noise: n must be at least 1");
+  long long off = 0;
+  for (int l = 0; l < levels; ++l) {
+    const long long items = n * m * (k[l] / 4);
+    const unsigned blocks = (unsigned)std::min<long long>((items + 255) / 256, 1 << 20);
+    umgm_noise_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(out + off, seed, l, n, m, k[l]);
+    off += n * m * k[l];
+  }
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+}  // extern "C"

@@ -668,6 +668,37 @@ int gencomm_v2v_aggregate_bwd(const float* dout, const double* theta, const int*
 long long gencomm_v2v_warp_pairs_bwd_scratch_floats(int P);
 int gencomm_v2v_warp_pairs_bwd(const float* dwarped, const double* theta, const int* src_row, const int* row_pair_off, const int* row_pairs,
                                float* dx, float* scratch, int P, int rows, int C, int H, int W, int accumulate, void* stream);
+/* CodeFilling codebook codec (opencood/models/sub_modules/codebook.py, UMGMQuantizer: a 1..3-level residual multi-codebook quantizer over
+ * rows of C channels); gencomm_amd/codebook.py is the module with the reference's state_dict keys; csrc/codebook_kernels.h has the kernel.
+ * Envelope: C 64 | 128 | 256, m 1 | 2 | 4, levels 1..3, k[l] a power of two in 16..256 (k: HOST array of `levels` ints); anything else is an
+ * argument error that names the argument.
+ *   params   gencomm_umgm_param_floats floats, per level: {latentStageEncoder, quantizationHead, latentHead, dequantizationHead, sideHead,
+ *            restoreHead} x (weight [C][C], bias [C]) -- the latentHead / sideHead slots of the last level are present and unread --, the
+ *            codebook [m][k][C / m], the temperature [m] padded to 4 floats
+ *   layout   HW == 0: x / restored are rows [n][C]; HW > 0: NCHW [n][C][HW] (n agents, n HW rows), read and written in place; keep (NCHW
+ *            only, may be null) [n] bytes: a non-zero entry makes that agent's restored map its input, bit for bit (code_loss is taken before)
+ *   gencomm_umgm_fwd         ONE launch for the whole codec plus a one-workgroup sum: restored, codes [levels][rows][m] int64 (argmax of the
+ *                            logits), sampled (may be null) the sampled indices in the same shape, logits [levels][rows, m, k_l] concatenated (null: never
+ *                            formed in memory), code_loss [1] =
+ *                            mean((restored - x)^2) through per-workgroup partial sums added in a fixed order (no float atomics: two runs
+ *                            give the same bits).  noise 0: the sampled index is the code; 1: uniforms [levels][rows, m, k_l] float32, the
+ *                            kernel applies clamp(eps, 1 - eps) and -log(-log u); 2: the uniforms are drawn in the kernel, Philox4x32-7
+ *                            keyed by `seed`, one counter per (level, row, group, codeword quad): independent of the tiling.
+ *                            workspace: gencomm_umgm_workspace_bytes(rows, C)
+ *   gencomm_umgm_noise_fwd   the uniforms noise 2 draws for `seed`, written as noise 1 reads them ([levels][n, m, k_l], n rows)
+ *   gencomm_umgm_encode_fwd  the reference's encode(): codes = argmin of the distance per level, residuals carried (same kernel, decoder off)
+ *   gencomm_umgm_decode_fwd  codes -> restored (same kernel, encoder off); a code outside 0 .. k - 1 is clamped
+ * -------------------------------------------------------------------------------------------- */
+long long gencomm_umgm_param_floats(int C, int m, const int* k, int levels);
+long long gencomm_umgm_workspace_bytes(long long rows, int C);
+int gencomm_umgm_fwd(const float* params, const float* x, const unsigned char* keep, const float* uniforms, unsigned long long seed, int noise,
+                     float* restored, long long* codes, long long* sampled, float* logits, float* code_loss, long long n, int HW, int C, int m,
+                     const int* k, int levels, void* workspace, long long workspace_bytes, void* stream);
+int gencomm_umgm_encode_fwd(const float* params, const float* x, long long* codes, long long n, int HW, int C, int m, const int* k, int levels,
+                            void* stream);
+int gencomm_umgm_decode_fwd(const float* params, const long long* codes, float* restored, long long n, int HW, int C, int m, const int* k, int levels,
+                            void* stream);
+int gencomm_umgm_noise_fwd(float* out, unsigned long long seed, long long n, int m, const int* k, int levels, void* stream);
 /* radix-3 split attention over the three window branches (sub_modules/split_attn.py:31-62): out = sum_r softmax_r(fc2(ReLU(LN(fc1(
  * mean_HW(a + b + c))))))[r] * branch_r (+ residual); fc1 [C][C], fc2 [3 C][C] without biases; scratch >= 4 n C floats; C <= 256 */
 int gencomm_split3_attn_fwd(const float* a, const float* b, const float* c, const float* fc1_w, const float* ln_w, const float* ln_b,
