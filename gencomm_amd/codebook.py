@@ -21,7 +21,12 @@ run reproducible; ``philox_uniforms(seed, n)`` exports the field); ``noise=False
 deterministic codec, and what ``decode(encode(x))`` restores.
 
 Supported envelope: channel 64 | 128 | 256; m 1 | 2 | 4; 1..3 levels; each k a power of two in 16..256; every component an
-``nn.Linear(channel, channel)``; ``permutationRate`` 0. Inference only: a grad-enabled call that would need a gradient raises.
+``nn.Linear(channel, channel)``; ``permutationRate`` 0. By default inference only: a grad-enabled call that would need a gradient raises.
+
+Training is opt-in: ``UMGMQuantizer(..., trainable=True)`` sends a grad-enabled ``forward`` / ``forward_map`` that needs a gradient through
+``codebook_bwd.UMGMFunction`` -- the same forward launch, and the straight-through backward ``gencomm_umgm_bwd``. ``restored`` and
+``code_loss`` are differentiable with respect to ``x``, the Linear heads, the tied codebooks and the temperatures; ``codes`` and ``logits``
+are marked non-differentiable (the baseline's shell discards both). ``encode`` / ``decode`` / ``pack`` stay inference-only.
 """
 from __future__ import annotations
 
@@ -87,8 +92,9 @@ def _linear(components, key, channel):
 
 class UMGMQuantizer(nn.Module):
     def __init__(self, channel: int, m: int, k: Union[int, List[int]], permutationRate: float,
-                 components: Dict[str, Callable[[], nn.Module]]):
+                 components: Dict[str, Callable[[], nn.Module]], trainable: bool = False):
         super().__init__()
+        self.trainable = bool(trainable)
         k = [k] if isinstance(k, int) else [int(v) for v in k]
         if channel not in CHANNELS:
             raise ValueError(f"UMGMQuantizer: channel {channel} is not supported (one of {list(CHANNELS)})")
@@ -166,8 +172,11 @@ class UMGMQuantizer(nn.Module):
         return self._blob
 
     # ------------------------------------------------------------------------------------- checks
+    def _needs_grad(self, x):
+        return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+
     def _refuse_grad(self, x):
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        if self._needs_grad(x):
             raise NotImplementedError("UMGMQuantizer: codebook training is not implemented (the straight-through backward of the fused codec); "
                                       "call under torch.no_grad(), or freeze the parameters and detach the input")
 
@@ -203,9 +212,9 @@ class UMGMQuantizer(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         return 2, None, int(seed)
 
-    def _run(self, x, rows, HW, keep, uniforms, seed, noise, with_logits, with_sampled=False):
+    def _run(self, x, rows, HW, keep, uniforms, seed, noise, with_logits, with_sampled=False, noise_args=None):
         dev, l, L, m = x.device, _lib.lib(), len(self._k), self._m
-        mode, u, seed = self._noise_args(rows, uniforms, seed, noise, dev)
+        mode, u, seed = noise_args if noise_args is not None else self._noise_args(rows, uniforms, seed, noise, dev)
         restored = torch.empty_like(x)
         codes = torch.empty((L, rows, m), dtype=torch.int64, device=dev)
         sampled = torch.empty_like(codes) if with_sampled else None
@@ -229,7 +238,12 @@ class UMGMQuantizer(nn.Module):
     def forward(self, x, uniforms: Optional[Sequence[torch.Tensor]] = None, seed: Optional[int] = None, noise: bool = True,
                 return_sampled: bool = False):
         """x [n, channel] -> (restored [n, channel], codes: L x [n, m] int64, logits: L x [n, m, k_i], code_loss), as the reference;
-        ``return_sampled`` appends the sampled indices (L x [n, m]), which the reference keeps to itself."""
+        ``return_sampled`` appends the sampled indices (L x [n, m]), which the reference keeps to itself. With ``trainable=True`` and a
+        gradient wanted, ``restored`` and ``code_loss`` carry it; ``codes`` and ``logits`` are non-differentiable."""
+        if self.trainable and self._needs_grad(x):
+            from .codebook_bwd import run_trainable
+            require_gpu(x, "UMGMQuantizer.forward")
+            return run_trainable(self, self._check_rows(x, "forward"), 0, None, uniforms, seed, noise, True, return_sampled)
         self._refuse_grad(x)
         x = self._check_rows(x, "forward")
         return self._run(x, x.shape[0], 0, None, uniforms, seed, noise, True, return_sampled)
@@ -240,13 +254,18 @@ class UMGMQuantizer(nn.Module):
         ``permute(...).contiguous()`` passes; row r of the rows entry is (agent, y, x) = (r // HW, (r % HW) // W, r % W). ``keep``: per-agent
         flags (bool tensor or sequence); a flagged agent's restored map is its input, bit for bit, while ``code_loss`` is the reference's
         (taken before the overwrite). Returns (restored NCHW, codes: L x [agents H W, m], logits or None, code_loss)."""
-        self._refuse_grad(x_nchw)
+        train = self.trainable and self._needs_grad(x_nchw)
+        if not train:
+            self._refuse_grad(x_nchw)
         x = self._check_map(x_nchw, "forward_map")
         A, _, H, W = x.shape
         if keep is not None:
             keep = torch.as_tensor(keep).to(device=x.device, dtype=torch.uint8).contiguous()
             if keep.numel() != A:
                 raise ValueError(f"UMGMQuantizer.forward_map: keep must have one flag per agent ({A}), got {keep.numel()}")
+        if train:   # a kept agent's g_restored goes straight to dx; its rows still receive the code_loss gradient through the codec
+            from .codebook_bwd import run_trainable
+            return run_trainable(self, x, H * W, keep, uniforms, seed, noise, return_logits, False)
         return self._run(x, A * H * W, H * W, keep, uniforms, seed, noise, return_logits)
 
     def encode(self, x) -> List[torch.Tensor]:

@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "codebook_bwd_kernels.h"
 #include "codebook_kernels.h"
 #include "iou3d_kernels.h"
 #include "loss_kernels.h"
@@ -1004,6 +1005,62 @@ int gencomm_umgm_noise_fwd(float* out, unsigned long long seed, long long n, int
   }
   GC_HIP(hipGetLastError());
   return GC_OK;
+}
+
+// ---- the codec's straight-through backward (codebook_bwd_kernels.h)
+long long gencomm_umgm_bwd_workspace_bytes(long long rows, int C, int m, const int* k, int levels) {
+  if (umgm_check_shape(C, m, k, levels) != GC_OK) return -1;
+  if (rows < 1) {
+    fail(GC_ERR_ARG, "umgm backward workspace: rows must be at least 1");
+    return -1;
+  }
+  return umgm_bwd_plan(rows, C, m, k, levels).total * (long long)sizeof(float);
+}
+
+int gencomm_umgm_bwd(const float* params, const float* x, const unsigned char* keep, const float* uniforms, unsigned long long seed, int noise,
+                     const long long* sampled, const float* d_restored, const float* d_loss, float* dx, float* dparams, int dx_only, long long n,
+                     int HW, int C, int m, const int* k, int levels, void* workspace, long long workspace_bytes, void* stream) {
+  if (int rc = umgm_check_shape(C, m, k, levels)) return rc;
+  GC_CHECK_ARG(params && x, "umgm backward: null pointer (params, x)");
+  GC_CHECK_ARG(sampled, "umgm backward: null pointer (sampled: the indices the forward returned)");
+  GC_CHECK_ARG(dx, "umgm backward: null pointer (dx)");
+  GC_CHECK_ARG(dx_only == 0 || dx_only == 1, "umgm backward: dx_only must be 0 or 1");
+  GC_CHECK_ARG(dx_only || dparams, "umgm backward: null pointer (dparams without dx_only)");
+  GC_CHECK_ARG(noise >= UMGM_NOISE_NONE && noise <= UMGM_NOISE_PHILOX, "umgm backward: noise must be 0 (none), 1 (uniforms) or 2 (Philox)");
+  GC_CHECK_ARG(noise != UMGM_NOISE_UNIFORMS || uniforms, "umgm backward: null pointer (uniforms with noise 1)");
+  GC_CHECK_ARG(keep == nullptr || HW > 0, "umgm backward: keep needs the NCHW entry (HW > 0)");
+  GC_CHECK_ARG(((((uintptr_t)params | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)d_restored | (uintptr_t)uniforms | (uintptr_t)dparams | (uintptr_t)workspace)) & 15) == 0,
+               "umgm backward: params, x, dx, d_restored, uniforms, dparams and workspace must be 16-byte aligned");
+  long long rows = 0;
+  if (int rc = umgm_rows(n, HW, &rows)) return rc;
+  const long long need = gencomm_umgm_bwd_workspace_bytes(rows, C, m, k, levels);
+  if (workspace == nullptr || workspace_bytes < need) return fail(GC_ERR_WORKSPACE, "umgm backward: workspace too small (gencomm_umgm_bwd_workspace_bytes)");
+  UmgmBwdArgs b{};
+  b.f.params = params; b.f.x = x; b.f.keep = keep; b.f.uniforms = uniforms; b.f.n = rows; b.f.seed = seed; b.f.HW = HW; b.f.m = m; b.f.L = levels;
+  b.f.task = UMGM_FORWARD; b.f.noise = noise;
+  b.sampled = sampled; b.d_restored = d_restored; b.d_loss = d_loss; b.dx = dx; b.dx_only = dx_only;
+  return umgm_bwd_launch(b, C, k, dparams, (float*)workspace, (hipStream_t)stream);
+}
+
+long long gencomm_rows_wgrad_fixed_scratch_floats(long long rows, int Co, int Ci) {
+  if (rows < 1 || Co < 64 || Ci < 64 || Co % 64 || Ci % 64 || Co > 4096 || Ci > 4096) {
+    fail(GC_ERR_ARG, "rows wgrad scratch: rows must be at least 1, Co and Ci multiples of 64 in 64 .. 4096");
+    return -1;
+  }
+  return rows_wgrad_scratch_floats(rows, Co, Ci, 1);
+}
+
+int gencomm_rows_wgrad_fixed(const float* g, const float* a, float* dw, long long rows, int Co, int Ci, float* scratch, long long scratch_floats,
+                             void* stream) {
+  GC_CHECK_ARG(g && a && dw, "rows wgrad: null pointer (g, a, dw)");
+  GC_CHECK_ARG(rows >= 1, "rows wgrad: rows must be at least 1");
+  GC_CHECK_ARG(Co >= 64 && Co <= 4096 && Co % 64 == 0, "rows wgrad: Co must be a multiple of 64 in 64 .. 4096");
+  GC_CHECK_ARG(Ci >= 64 && Ci <= 4096 && Ci % 64 == 0, "rows wgrad: Ci must be a multiple of 64 in 64 .. 4096");
+  if (scratch == nullptr || scratch_floats < rows_wgrad_scratch_floats(rows, Co, Ci, 1))
+    return fail(GC_ERR_WORKSPACE, "rows wgrad: scratch too small (gencomm_rows_wgrad_fixed_scratch_floats)");
+  RowsWgradArgs w{};
+  w.G[0] = g; w.A[0] = a; w.out[0] = dw; w.part = scratch; w.rows = rows; w.Co = Co; w.Ci = Ci; w.count = 1;
+  return rows_wgrad_launch(w, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -699,6 +699,29 @@ int gencomm_umgm_encode_fwd(const float* params, const float* x, long long* code
 int gencomm_umgm_decode_fwd(const float* params, const long long* codes, float* restored, long long n, int HW, int C, int m, const int* k, int levels,
                             void* stream);
 int gencomm_umgm_noise_fwd(float* out, unsigned long long seed, long long n, int m, const int* k, int levels, void* stream);
+/* Straight-through backward of the codec: the gradient of (restored, code_loss) of a gencomm_umgm_fwd call with respect to x and to
+ * every parameter. The forward of the trainable path IS gencomm_umgm_fwd with `sampled` requested; the backward recomputes the forward's
+ * intermediates per 64-row tile and takes the one-hot from `sampled` (an argmax is never re-decided). No float atomics: two calls give
+ * the same bits.
+ *   params, x, keep, uniforms, seed, noise, n, HW, C, m, k, levels   as the forward call got them (noise 0: p = softmax(logit))
+ *   sampled      [levels][rows][m] int64, what the forward returned
+ *   d_restored   layout of x, may be null; a kept agent's part goes straight to dx
+ *   d_loss       DEVICE pointer to one float, may be null (no host read)
+ *   dx           layout of x, every element written once
+ *   dparams      gencomm_umgm_param_floats floats in the order of params, every slot written (the unread latentHead / sideHead slots of
+ *                the last level and the temperature padding: zeros); the temperature's gradient has gone through LowerBound's rule
+ *                (passes where temperature >= 1e-6 or the gradient is negative). May be null with dx_only.
+ *   dx_only      1: skip all parameter-gradient work (a frozen codec that passes gradients through)
+ *   workspace    gencomm_umgm_bwd_workspace_bytes(rows, C, m, k, levels), 16-byte aligned
+ * gencomm_rows_wgrad_fixed: dw [Co][Ci] = g^T a over rows, g [rows][Co], a [rows][Ci] row-major, on the fp32 matrix pipe; row ranges
+ * are summed in a fixed order. Co, Ci multiples of 64 in 64 .. 4096; scratch: gencomm_rows_wgrad_fixed_scratch_floats floats. */
+long long gencomm_umgm_bwd_workspace_bytes(long long rows, int C, int m, const int* k, int levels);
+int gencomm_umgm_bwd(const float* params, const float* x, const unsigned char* keep, const float* uniforms, unsigned long long seed, int noise,
+                     const long long* sampled, const float* d_restored, const float* d_loss, float* dx, float* dparams, int dx_only, long long n,
+                     int HW, int C, int m, const int* k, int levels, void* workspace, long long workspace_bytes, void* stream);
+long long gencomm_rows_wgrad_fixed_scratch_floats(long long rows, int Co, int Ci);
+int gencomm_rows_wgrad_fixed(const float* g, const float* a, float* dw, long long rows, int Co, int Ci, float* scratch, long long scratch_floats,
+                             void* stream);
 /* radix-3 split attention over the three window branches (sub_modules/split_attn.py:31-62): out = sum_r softmax_r(fc2(ReLU(LN(fc1(
  * mean_HW(a + b + c))))))[r] * branch_r (+ residual); fc1 [C][C], fc2 [3 C][C] without biases; scratch >= 4 n C floats; C <= 256 */
 int gencomm_split3_attn_fwd(const float* a, const float* b, const float* c, const float* fc1_w, const float* ln_w, const float* ln_b,
