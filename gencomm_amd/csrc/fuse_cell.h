@@ -1,15 +1,27 @@
-// The bilinear cell and tap arithmetic of warp_affine_simple (opencood/models/sub_modules/torch_transformation_utils.py:323-332), shared
-// by the fusion kernels (fusion_kernels.h) and the V2VNet message-passing kernels (v2v_kernels.h), which live in different translation
-// units: device functions only, no kernel is defined here.
+// warp_affine_simple (opencood/models/sub_modules/torch_transformation_utils.py:323-332), written once: the sampling position of an
+// output pixel, its bilinear cell and its taps.  Every kernel that warps an agent map into the ego frame calls these -- the fusion
+// kernels (fusion_kernels.h: attention, max, token-major, their backwards), the V2VNet message-passing kernels (v2v_kernels.h) and
+// warp_affine_kernel / warp_affine_bwd_kernel (v2xvit_kernels.h: V2X-ViT, where2comm, CoBEVT) -- which live in different translation
+// units: device functions only, no kernel is defined here.  The max backward recomputes the forward's winners and the gather passes
+// re-derive the forward's cells from them, so the layers below are the only place this arithmetic may be written.
+//   fuse_base      affine_grid's base coordinate of an index
+//   fuse_point     sampling position: north-west corner + fractions; false = far outside
+//   fuse_cell_geo  + the four corners clamped into the map and their validity mask
+//   fuse_cell      + the four tap weights
+//   fuse_sample    one warped value from a cell
 #pragma once
 #include "common.h"
 
 namespace gc {
 
-// Bilinear cell of one (output pixel, agent), shared by the forward (both modes) and by the max backward's winner recomputation:
-// float64 affine grid rounded to float32, grid_sampler unnormalize (align_corners=False), the four corners clamped into the map.
-__device__ __forceinline__ void fuse_cell(const double* __restrict__ th, double xb, double yb, int H, int W, int (&idx)[4], unsigned& ok,
-                                          float (&wt)[4]) {
+// affine_grid base coordinate of index i on an axis of `size`, align_corners=False: (2i+1)/size - 1, in float64 like theta
+__device__ __forceinline__ double fuse_base(int i, int size) { return (2.0 * i + 1.0) / (double)size - 1.0; }
+
+// Sampling position of one (output pixel, agent): float64 affine grid rounded to float32, grid_sampler unnormalize
+// (align_corners=False), the north-west corner (x0, y0) clamped into [-2, size + 1] and the fractions.  False when the clamp moved the
+// corner: the agent is far away and everything is out of range.
+__device__ __forceinline__ bool fuse_point(const double* __restrict__ th, double xb, double yb, int H, int W, int& x0, int& y0, float& tx,
+                                           float& ty) {
   const float gx = (float)(th[0] * xb + th[1] * yb + th[2]);
   const float gy = (float)(th[3] * xb + th[4] * yb + th[5]);
   // grid_sampler unnormalize (align_corners=False): ((g + 1) * size - 1) / 2
@@ -17,19 +29,33 @@ __device__ __forceinline__ void fuse_cell(const double* __restrict__ th, double 
   const float iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
   const float fx = floorf(ix), fy = floorf(iy);
   // keep the integer conversion in range for far-away agents
-  const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f);
-  const int y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
-  const float tx = ix - fx, ty = iy - fy;  // == ix - ix_nw etc.
-  const float wnw = (1.f - tx) * (1.f - ty), wne = tx * (1.f - ty), wsw = (1.f - tx) * ty, wse = tx * ty;
+  x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f);
+  y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
+  tx = ix - fx; ty = iy - fy;  // == ix - ix_nw etc.
+  return !(fx != (float)x0 || fy != (float)y0);
+}
+
+// Bilinear cell of one (output pixel, agent) without the weights: the four corners clamped into the map, the 4-bit mask of the valid
+// ones (zero for a dead pixel, !live, and for a far-away agent) and the fractions.
+__device__ __forceinline__ void fuse_cell_geo(const double* __restrict__ th, double xb, double yb, int H, int W, bool live, int (&idx)[4],
+                                              unsigned& ok, float& tx, float& ty) {
+  int x0, y0;
+  const bool in = fuse_point(th, xb, yb, H, W, x0, y0, tx, ty) && live;
   const bool xl = x0 >= 0 && x0 < W, xr = x0 + 1 >= 0 && x0 + 1 < W;
   const bool yt = y0 >= 0 && y0 < H, yb_ = y0 + 1 >= 0 && y0 + 1 < H;
-  const bool far = fx != (float)x0 || fy != (float)y0;  // clamped => everything out of range
   // every tap is LOADED, from the corner clamped into the map, and an invalid one is replaced by an exact zero afterwards: with a
   // branch per tap the loads of a channel were issued one memory latency after the other (the token-major kernel's lesson)
   const int xc0 = min(max(x0, 0), W - 1), xc1 = min(max(x0 + 1, 0), W - 1), yc0 = min(max(y0, 0), H - 1), yc1 = min(max(y0 + 1, 0), H - 1);
   idx[0] = yc0 * W + xc0; idx[1] = yc0 * W + xc1; idx[2] = yc1 * W + xc0; idx[3] = yc1 * W + xc1;
-  ok = (xl && yt && !far ? 1u : 0u) | (xr && yt && !far ? 2u : 0u) | (xl && yb_ && !far ? 4u : 0u) | (xr && yb_ && !far ? 8u : 0u);
-  wt[0] = wnw; wt[1] = wne; wt[2] = wsw; wt[3] = wse;
+  ok = (in && xl && yt ? 1u : 0u) | (in && xr && yt ? 2u : 0u) | (in && xl && yb_ ? 4u : 0u) | (in && xr && yb_ ? 8u : 0u);
+}
+
+// Bilinear cell of one (output pixel, agent), shared by the forwards, their backwards and the max backward's winner recomputation.
+__device__ __forceinline__ void fuse_cell(const double* __restrict__ th, double xb, double yb, int H, int W, int (&idx)[4], unsigned& ok,
+                                          float (&wt)[4]) {
+  float tx, ty;
+  fuse_cell_geo(th, xb, yb, H, W, true, idx, ok, tx, ty);
+  wt[0] = (1.f - tx) * (1.f - ty); wt[1] = tx * (1.f - ty); wt[2] = (1.f - tx) * ty; wt[3] = tx * ty;
 }
 
 // One warped value: the four taps of a cell, an invalid tap contributing an exact zero (fixed fma order: the max backward recomputes
@@ -48,11 +74,11 @@ __device__ __forceinline__ float fuse_sample(const float* __restrict__ plane, co
 constexpr int FUSE_KM = 12;
 
 // Every output pixel p whose bilinear cell (agent transform th) contains the source pixel (qx, qy), with its tap weight: f(p, wgt).
-// Candidates = a window around q's pre-image (float64); each candidate's cell is recomputed with exactly fuse_body's arithmetic.
+// Candidates = a window around q's pre-image (float64); each candidate's sampling position is fuse_point's, as in the forward.
 // Shared by the gather passes of the attention backward and of the max backward.
 template <class F>
 __device__ __forceinline__ void fuse_for_each_match(const double* __restrict__ th, int qx, int qy, int H, int W, F&& f) {
-  const double gx = (2.0 * qx + 1.0) / (double)W - 1.0, gy = (2.0 * qy + 1.0) / (double)H - 1.0;
+  const double gx = fuse_base(qx, W), gy = fuse_base(qy, H);
   const double det = th[0] * th[4] - th[1] * th[3];
   const double xb = (th[4] * (gx - th[2]) - th[1] * (gy - th[5])) / det, yb = (-th[3] * (gx - th[2]) + th[0] * (gy - th[5])) / det;
   const double pxf = ((xb + 1.0) * W - 1.0) * 0.5, pyf = ((yb + 1.0) * H - 1.0) * 0.5;
@@ -60,16 +86,11 @@ __device__ __forceinline__ void fuse_for_each_match(const double* __restrict__ t
   const int y_lo = max((int)floor(pyf - 1.6), 0), y_hi = min((int)ceil(pyf + 1.6), H - 1);
   for (int py = y_lo; py <= y_hi; ++py)
     for (int px = x_lo; px <= x_hi; ++px) {
-      const double oxb = (2.0 * px + 1.0) / (double)W - 1.0, oyb = (2.0 * py + 1.0) / (double)H - 1.0;
-      const float sgx = (float)(th[0] * oxb + th[1] * oyb + th[2]);
-      const float sgy = (float)(th[3] * oxb + th[4] * oyb + th[5]);
-      const float ix = ((sgx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((sgy + 1.f) * (float)H - 1.f) * 0.5f;
-      const float fx = floorf(ix), fy = floorf(iy);
-      const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f), y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
-      if (fx != (float)x0 || fy != (float)y0) continue;   // clamped: everything out of range
+      int x0, y0;
+      float tx, ty;
+      if (!fuse_point(th, fuse_base(px, W), fuse_base(py, H), H, W, x0, y0, tx, ty)) continue;   // far: everything out of range
       const int dx = qx - x0, dy = qy - y0;
       if (dx < 0 || dx > 1 || dy < 0 || dy > 1) continue;
-      const float tx = ix - fx, ty = iy - fy;
       const float wgt = (dx ? tx : 1.f - tx) * (dy ? ty : 1.f - ty);
       if (wgt == 0.f) continue;
       f(py * W + px, wgt);

@@ -11,7 +11,7 @@
 // both channel passes (scores, then weighted sum).  Pure gather, HBM/L2-bound.
 #pragma once
 #include "common.h"
-#include "fuse_cell.h"   // fuse_cell / fuse_sample: the bilinear cell and tap arithmetic, shared with v2v_kernels.h
+#include "fuse_cell.h"   // warp_affine_simple's cell and tap arithmetic, shared with v2v_kernels.h and v2xvit_kernels.h
 
 namespace gc {
 
@@ -33,9 +33,7 @@ __device__ __forceinline__ void fuse_body(const FuseArgs& a, int b, int off, int
   const bool live = pix_raw < HW;
   const int pix = live ? pix_raw : HW - 1;
   const int h = pix / W, w = pix - h * W;
-  // affine_grid base coordinates, align_corners=False: (2i+1)/size - 1, in float64 like theta
-  const double xb = (2.0 * w + 1.0) / (double)W - 1.0;
-  const double yb = (2.0 * h + 1.0) / (double)H - 1.0;
+  const double xb = fuse_base(w, W), yb = fuse_base(h, H);
   int idx[N][4];
   unsigned ok[N];
   float wt[N][4];
@@ -155,7 +153,7 @@ inline int warp_attfuse_enqueue(const float* x, const double* theta, const int* 
 
 // ---------------------------------------------------------------------------------------------
 // Backward of warp + ego-row attention (training: the detection loss back-propagates through AttFusion into the Enhancer
-// and GenComm).  One lane per OUTPUT pixel, same taps as the forward:
+// and GenComm).  One lane per OUTPUT pixel, the forward's taps from the forward's own fuse_cell / fuse_sample:
 //   w = softmax(s), s_j = <x_0, x_j> / sqrt(C), out = sum_j w_j x_j
 //   d w_j = <g, x_j>,  d s_j = w_j (d w_j - sum_k w_k d w_k) / sqrt(C)
 //   d x_j = w_j g + d s_j x_0  (j != 0),   d x_0 = w_0 g + sum_j d s_j x_j + d s_0 x_0
@@ -183,41 +181,13 @@ __device__ __forceinline__ void fuse_bwd_body(const FuseBwdArgs& a, int b, int o
   const bool live = pix_raw < HW;
   const int pix = live ? pix_raw : HW - 1;
   const int h = pix / W, w = pix - h * W;
-  const double xb = (2.0 * w + 1.0) / (double)W - 1.0;
-  const double yb = (2.0 * h + 1.0) / (double)H - 1.0;
+  const double xb = fuse_base(w, W), yb = fuse_base(h, H);
   int idx[N][4];
   unsigned ok[N];
   float wt[N][4];
 #pragma unroll
-  for (int j = 0; j < N; ++j) {  // identical to fuse_body's tap computation
-    const double* __restrict__ th = a.theta + (size_t)(off + j) * 6;
-    const float gx = (float)(th[0] * xb + th[1] * yb + th[2]);
-    const float gy = (float)(th[3] * xb + th[4] * yb + th[5]);
-    const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f;
-    const float iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f);
-    const int y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
-    const float tx = ix - fx, ty = iy - fy;
-    const bool xl = x0 >= 0 && x0 < W, xr = x0 + 1 >= 0 && x0 + 1 < W;
-    const bool yt = y0 >= 0 && y0 < H, yb_ = y0 + 1 >= 0 && y0 + 1 < H;
-    const bool far = fx != (float)x0 || fy != (float)y0;
-    // every tap is LOADED, from the corner clamped into the map, and an invalid one is replaced by an exact zero afterwards: with a
-    // branch per tap the loads of a channel were issued one memory latency after the other (the token-major kernel's lesson)
-    const int xc0 = min(max(x0, 0), W - 1), xc1 = min(max(x0 + 1, 0), W - 1), yc0 = min(max(y0, 0), H - 1), yc1 = min(max(y0 + 1, 0), H - 1);
-    idx[j][0] = yc0 * W + xc0; idx[j][1] = yc0 * W + xc1; idx[j][2] = yc1 * W + xc0; idx[j][3] = yc1 * W + xc1;
-    ok[j] = (xl && yt && !far ? 1u : 0u) | (xr && yt && !far ? 2u : 0u) | (xl && yb_ && !far ? 4u : 0u) | (xr && yb_ && !far ? 8u : 0u);
-    wt[j][0] = (1.f - tx) * (1.f - ty); wt[j][1] = tx * (1.f - ty); wt[j][2] = (1.f - tx) * ty; wt[j][3] = tx * ty;
-  }
-  auto sample = [&](int j, const float* __restrict__ plane) {
-    float t[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] = plane[idx[j][k]];
-    float v = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v = fmaf((ok[j] >> k) & 1u ? t[k] : 0.f, wt[j][k], v);
-    return v;
-  };
+  for (int j = 0; j < N; ++j) fuse_cell(a.theta + (size_t)(off + j) * 6, xb, yb, H, W, idx[j], ok[j], wt[j]);
+  auto sample = [&](int j, const float* __restrict__ plane) { return fuse_sample(plane, idx[j], ok[j], wt[j]); };
   const float* __restrict__ xs = a.x + (size_t)off * a.C * HW;
   const float* __restrict__ gp = a.gout + (size_t)b * a.C * HW + pix;
   float score[N], dw[N];
@@ -493,8 +463,7 @@ __device__ __forceinline__ void maxfuse_bwd_body(const MaxBwdArgs& a, int b, int
   const int H = a.H, W = a.W, HW = H * W;
   if (pix >= HW) return;   // no barrier in this kernel
   const int h = pix / W, w = pix - h * W;
-  const double xb = (2.0 * w + 1.0) / (double)W - 1.0;
-  const double yb = (2.0 * h + 1.0) / (double)H - 1.0;
+  const double xb = fuse_base(w, W), yb = fuse_base(h, H);
   int idx[N][4];
   unsigned ok[N];
   float wt[N][4];
@@ -638,8 +607,7 @@ struct FuseTokArgs {
   int xcd;               // 1: XCD-aware block order (MODE_XCD_REMAP)
 };
 
-// bilinear cell of one (output pixel, agent): the four corner pixels CLAMPED into the map (every corner is loaded, without a branch:
-// with a branch per corner the loads of a pass were issued one latency after the other), fractions, valid corners
+// fuse_cell_geo's result for one (output pixel, agent): the four corner pixels clamped into the map, fractions, valid corners
 struct __align__(16) FuseGeo { int idx[4]; float tx, ty; unsigned mask, pad; };
 
 template <int N, int QPL /*float4 quads per lane*/>
@@ -653,23 +621,8 @@ __device__ __forceinline__ void fuse_tok_body(const FuseTokArgs& a, int bx, int 
     const int pix = bx * 64 + pl;
     const bool ok = pix < HW;
     const int h = ok ? pix / W : 0, w = ok ? pix - h * W : 0;
-    const double xb = (2.0 * w + 1.0) / (double)W - 1.0, yb = (2.0 * h + 1.0) / (double)H - 1.0;
-    const double* __restrict__ th = a.theta + (size_t)(off + j) * 6;
-    const float gx = (float)(th[0] * xb + th[1] * yb + th[2]);
-    const float gy = (float)(th[3] * xb + th[4] * yb + th[5]);
-    const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f), y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
-    const bool far = fx != (float)x0 || fy != (float)y0;
-    const bool xl = x0 >= 0 && x0 < W, xr = x0 + 1 >= 0 && x0 + 1 < W;
-    const bool yt = y0 >= 0 && y0 < H, yb_ = y0 + 1 >= 0 && y0 + 1 < H;
-    const bool in = ok && !far;
     FuseGeo g;
-    const int xc0 = min(max(x0, 0), W - 1), xc1 = min(max(x0 + 1, 0), W - 1), yc0 = min(max(y0, 0), H - 1), yc1 = min(max(y0 + 1, 0), H - 1);
-    g.idx[0] = yc0 * W + xc0; g.idx[1] = yc0 * W + xc1; g.idx[2] = yc1 * W + xc0; g.idx[3] = yc1 * W + xc1;
-    g.tx = ix - fx;
-    g.ty = iy - fy;
-    g.mask = (in && xl && yt ? 1u : 0u) | (in && xr && yt ? 2u : 0u) | (in && xl && yb_ ? 4u : 0u) | (in && xr && yb_ ? 8u : 0u);
+    fuse_cell_geo(a.theta + (size_t)(off + j) * 6, fuse_base(w, W), fuse_base(h, H), H, W, ok, g.idx, g.mask, g.tx, g.ty);
     g.pad = 0u;
     s_geo[j][pl] = g;
   }

@@ -64,8 +64,7 @@ __global__ __launch_bounds__(256) void v2v_warp_pairs_kernel(const V2vWarpArgs a
     return;
   }
   const int h = pix / W, w = pix - h * W;
-  const double xb = (2.0 * w + 1.0) / (double)W - 1.0;
-  const double yb = (2.0 * h + 1.0) / (double)H - 1.0;
+  const double xb = fuse_base(w, W), yb = fuse_base(h, H);
   int idx[4];
   unsigned ok;
   float wt[4];
@@ -138,8 +137,7 @@ __global__ __launch_bounds__(256) void v2v_aggregate_kernel(const V2vAggArgs a) 
     for (int i = 0; i < V; ++i) {
       const int pix = pix0 + i;
       const int hh = pix / W, ww = pix - hh * W;
-      const double xb = (2.0 * ww + 1.0) / (double)W - 1.0;
-      const double yb = (2.0 * hh + 1.0) / (double)H - 1.0;
+      const double xb = fuse_base(ww, W), yb = fuse_base(hh, H);
       int idx[4];
       unsigned ok;
       float wt[4];
@@ -242,8 +240,7 @@ __global__ __launch_bounds__(256) void v2v_aggregate_bwd_kernel(const V2vAggBwdA
     for (int i = 0; i < V; ++i) {
       const int pix = pix0 + i;
       const int hh = pix / W, ww = pix - hh * W;
-      const double xb = (2.0 * ww + 1.0) / (double)W - 1.0;
-      const double yb = (2.0 * hh + 1.0) / (double)H - 1.0;
+      const double xb = fuse_base(ww, W), yb = fuse_base(hh, H);
       int idx[4];
       unsigned ok;
       float wt[4];
@@ -414,8 +411,7 @@ __global__ __launch_bounds__(256) void v2v_warp_bwd_scatter_kernel(const V2vWarp
   const int pix = blockIdx.x * 64 + pl;
   if (pix >= HW) return;
   const int h = pix / W, w = pix - h * W;
-  const double xb = (2.0 * w + 1.0) / (double)W - 1.0;
-  const double yb = (2.0 * h + 1.0) / (double)H - 1.0;
+  const double xb = fuse_base(w, W), yb = fuse_base(h, H);
   int idx[4];
   unsigned ok;
   float wt[4];

@@ -2,7 +2,8 @@
 // sub_modules/{v2xvit_basic, hmsa, mswin, split_attn, base_transformer}.py) -- the kernels that have no counterpart elsewhere
 // in the library.  Activations are NCHW fp32 per agent, [sumN][C][H][W]; the Linear layers run as 1x1 convolutions on the
 // general implicit-GEMM kernel (conv_kernels.h), LayerNorm on ln_nchw_fwd_kernel (train_kernels.h).
-//   warp_affine_kernel   warp_affine_simple (torch_transformation_utils.py:323-332): every agent into the ego frame
+//   warp_affine_kernel   warp_affine_simple (torch_transformation_utils.py:323-332): every agent into the ego frame, one lane per
+//                        pixel on fuse_cell / fuse_sample (fuse_cell.h) -- the fusion kernels' cell, bit for bit
 //   hgt_attn_kernel      HGTCavAttention's core (hmsa.py:117-150): per pixel and head, attention ACROSS the agents of a scene.
 //                        GenComm passes an all-zero prior encoding, so every agent has type 0 and a single relation: the host
 //                        folds relation_att into the key projection and relation_msg into the value projection, which leaves a
@@ -12,6 +13,7 @@
 // fp32 throughout; softmax with the running maximum; one lane per query.
 #pragma once
 #include "common.h"
+#include "fuse_cell.h"
 
 namespace gc {
 
@@ -26,30 +28,13 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const WarpArgs a) {
   const int H = a.H, W = a.W, HW = H * W;
   if (pix >= HW) return;
   const int h = pix / W, w = pix - h * W;
-  const double xb = (2.0 * w + 1.0) / (double)W - 1.0, yb = (2.0 * h + 1.0) / (double)H - 1.0;  // affine_grid, align_corners=False, float64
-  const double* __restrict__ th = a.theta + (size_t)n * 6;
-  const float gx = (float)(th[0] * xb + th[1] * yb + th[2]);
-  const float gy = (float)(th[3] * xb + th[4] * yb + th[5]);
-  const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f), y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
-  const float tx = ix - fx, ty = iy - fy;
-  const bool far = fx != (float)x0 || fy != (float)y0;
-  const bool xl = x0 >= 0 && x0 < W, xr = x0 + 1 >= 0 && x0 + 1 < W, yt = y0 >= 0 && y0 < H, yb_ = y0 + 1 >= 0 && y0 + 1 < H;
-  const int i0 = (xl && yt && !far) ? y0 * W + x0 : -1, i1 = (xr && yt && !far) ? y0 * W + x0 + 1 : -1;
-  const int i2 = (xl && yb_ && !far) ? (y0 + 1) * W + x0 : -1, i3 = (xr && yb_ && !far) ? (y0 + 1) * W + x0 + 1 : -1;
-  const float w0 = (1.f - tx) * (1.f - ty), w1 = tx * (1.f - ty), w2 = (1.f - tx) * ty, w3 = tx * ty;
+  int idx[4];
+  unsigned ok;
+  float wt[4];
+  fuse_cell(a.theta + (size_t)n * 6, fuse_base(w, W), fuse_base(h, H), H, W, idx, ok, wt);
   const float* __restrict__ xp = a.x + (size_t)n * a.C * HW;
   float* __restrict__ op = a.out + (size_t)n * a.C * HW + pix;
-  for (int c = 0; c < a.C; ++c) {
-    const float* __restrict__ pl = xp + (size_t)c * HW;
-    float v = 0.f;
-    v = fmaf(i0 >= 0 ? pl[i0] : 0.f, w0, v);
-    v = fmaf(i1 >= 0 ? pl[i1] : 0.f, w1, v);
-    v = fmaf(i2 >= 0 ? pl[i2] : 0.f, w2, v);
-    v = fmaf(i3 >= 0 ? pl[i3] : 0.f, w3, v);
-    op[(size_t)c * HW] = v;
-  }
+  for (int c = 0; c < a.C; ++c) op[(size_t)c * HW] = fuse_sample(xp + (size_t)c * HW, idx, ok, wt);
 }
 
 // qkv [n][3*inner][HW] (q | k' | v' blocks of `inner` = heads * DH channels, head-major) -> out [n][inner][HW]
@@ -442,24 +427,17 @@ __global__ __launch_bounds__(256) void warp_affine_bwd_kernel(const WarpArgs a /
   const int H = a.H, W = a.W, HW = H * W;
   if (pix >= HW) return;
   const int h = pix / W, w = pix - h * W;
-  const double xb = (2.0 * w + 1.0) / (double)W - 1.0, yb = (2.0 * h + 1.0) / (double)H - 1.0;
-  const double* __restrict__ th = a.theta + (size_t)n * 6;
-  const float gx = (float)(th[0] * xb + th[1] * yb + th[2]);
-  const float gy = (float)(th[3] * xb + th[4] * yb + th[5]);
-  const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
-  const float fx = floorf(ix), fy = floorf(iy);
-  if (!(fx >= -1.f && fx <= (float)W && fy >= -1.f && fy <= (float)H)) return;   // all four corners outside
-  const int x0 = (int)fx, y0 = (int)fy;
-  const float tx = ix - fx, ty = iy - fy;
-  const bool xl = x0 >= 0 && x0 < W, xr = x0 + 1 >= 0 && x0 + 1 < W, yt = y0 >= 0 && y0 < H, yb_ = y0 + 1 >= 0 && y0 + 1 < H;
-  const float w00 = (1.f - tx) * (1.f - ty), w01 = tx * (1.f - ty), w10 = (1.f - tx) * ty, w11 = tx * ty;
+  int idx[4];
+  unsigned ok;
+  float wt[4];
+  fuse_cell(a.theta + (size_t)n * 6, fuse_base(w, W), fuse_base(h, H), H, W, idx, ok, wt);
+  if (ok == 0u) return;   // all four corners outside
   for (int c = 0; c < a.C; ++c) {
     const float g = dout[((size_t)n * a.C + c) * HW + pix];
     float* __restrict__ d = a.out + ((size_t)n * a.C + c) * HW;
-    if (xl && yt) atomicAdd(&d[y0 * W + x0], w00 * g);
-    if (xr && yt) atomicAdd(&d[y0 * W + x0 + 1], w01 * g);
-    if (xl && yb_) atomicAdd(&d[(y0 + 1) * W + x0], w10 * g);
-    if (xr && yb_) atomicAdd(&d[(y0 + 1) * W + x0 + 1], w11 * g);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if ((ok >> k) & 1u) atomicAdd(&d[idx[k]], wt[k] * g);
   }
 }
 

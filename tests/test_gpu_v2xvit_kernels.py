@@ -7,7 +7,8 @@ operation in float64 (tests/v2xvit_kernel_reference.py):
   agent attention   gencomm_hgt_attn_fwd at dim_head 8 .. 64 with scenes of 1 .. 8 agents in one launch, per-query-agent and streaming
                     form; gencomm_hgt_attn_bwd at dim_head 8, 16, 64
   warp              gencomm_warp_affine_fwd / _bwd: identity, whole-pixel shift, rotation, sampling positions within a pixel of each
-                    border, maps sent far outside
+                    border, maps sent far outside; the same thetas through gencomm_warp_maxfuse_fwd / gencomm_warp_attfuse_fwd with one
+                    agent per scene, bit for bit the warp's output (one bilinear cell for every kernel, csrc/fuse_cell.h)
   split attention   gencomm_split3_attn_fwd at C 64 / 96 / 128 / 256, with and without the residual
   contract          argument errors, and the 8-agents-per-scene limit of the module
 
@@ -316,6 +317,37 @@ def test_warp_affine_fwd_bwd(H, W, C):
             assert torch.equal(o[1], shifted), "whole-pixel shift is not bit-exact"
     finally:
         rep.show()
+
+
+@pytest.mark.parametrize("H,W,C", [(13, 22, 5), (16, 16, 3)])
+def test_warp_is_one_cell_across_kernels(H, W, C):
+    """warp_affine_kernel, warp_attfuse_kernel in max mode and in attention mode sample with one bilinear cell (csrc/fuse_cell.h): with
+    every agent a scene of its own the three outputs are the same bits -- the max of one map is that map, and the attention weight of a
+    single agent is exp(0) / exp(0) = 1 with fmaf(1, v, 0) = v.  x has no zeros, so a tap dropped or added by one kernel shows."""
+    names = list(_thetas(H, W))
+    theta = torch.tensor([_thetas(H, W)[k] for k in names], dtype=torch.float64)
+    n = len(names)
+    assert sum(k.startswith("far") for k in names) == 2
+    seen = [0, 0, 0, 0]
+    for i, k in enumerate(names):
+        if "band" in k:
+            seen = [a + b for a, b in zip(seen, _border_bands(theta[i], H, W))]
+    assert min(seen) > 0, seen          # each single out-of-range side is sampled
+    g = torch.Generator().manual_seed(3 * H * W + C)
+    x = torch.randn(n, C, H, W, generator=g)
+    x = torch.where(x == 0, torch.ones_like(x), x)
+    th_d, x_d = theta.to(_dev()), x.to(_dev())
+    scene_off = torch.arange(n + 1, dtype=torch.int32, device=_dev())
+    warp, mx, att = Guarded(x.shape), Guarded(x.shape), Guarded(x.shape)
+    _call("gencomm_warp_affine_fwd", _p(x_d), _p(th_d), _p(warp.t), n, C, H, W, _st())
+    _call("gencomm_warp_maxfuse_fwd", _p(x_d), _p(th_d), _p(scene_off), _p(mx.t), n, n, C, H, W, _st())
+    _call("gencomm_warp_attfuse_fwd", _p(x_d), _p(th_d), _p(scene_off), _p(att.t), n, n, C, H, W, _st())
+    assert warp.intact() and mx.intact() and att.intact()
+    o = warp.t.cpu()
+    assert bool(torch.isfinite(o).all()) and float(o[0].abs().max()) > 0
+    for i, k in enumerate(names):
+        assert torch.equal(mx.t[i].cpu(), o[i]), f"max fusion differs from warp_affine [{k}]"
+        assert torch.equal(att.t[i].cpu(), o[i]), f"attention fusion differs from warp_affine [{k}]"
 
 
 # ---- split attention --------------------------------------------------------------------------------------------------------------
