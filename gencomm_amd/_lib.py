@@ -227,6 +227,15 @@ def library_src_hash() -> str:
     return info.rsplit(" src=", 1)[1] if " src=" in info else ""
 
 
+# The compile flags of every translation unit (tools/resource_usage.py compiles with the same list).
+# -packed-fp32-ops: no v_pk_{fma,mul,add}_f32. With them, conv8h_kernel's epilogue `acc * inv_scale + bias` compiled to
+# `v_pk_fma_f32 v[0:1], v[0:1], s[22:23], v[22:23] op_sel:[0,0,1]` and sporadically lost the bias in the low half on
+# lanes 48..63 whenever two workgroups shared a SIMD (never with one workgroup per CU); the same source built
+# without packed ops is exact in every run (tools/conv8_unit.py), and the hot kernels are not slower for it.
+HIP_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
+             "-Wno-unused-function", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP library in-tree for gfx950 (cross-compiles without a GPU)."""
     srcs = hip_sources()
@@ -234,12 +243,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    # -packed-fp32-ops: no v_pk_{fma,mul,add}_f32. With them, conv8h_kernel's epilogue `acc * inv_scale + bias` compiled to
-    # `v_pk_fma_f32 v[0:1], v[0:1], s[22:23], v[22:23] op_sel:[0,0,1]` and sporadically lost the bias in the low half on
-    # lanes 48..63 whenever two workgroups shared a SIMD (never with one workgroup per CU); the same source built
-    # without packed ops is exact in every run (tools/conv8_unit.py), and the hot kernels are not slower for it.
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
-             "-Wno-unused-function", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+    flags = list(HIP_FLAGS)
     # diagnostic builds (A/B variants under tools/): GENCOMM_HIP_LIB names the output, GENCOMM_EXTRA_FLAGS adds -D switches; such a
     # library carries its switches in gencomm_build_info() and a different source stamp is not needed (the flags differ)
     extra = os.environ.get("GENCOMM_EXTRA_FLAGS", "").split()

@@ -6,6 +6,7 @@
 // so memory is O(N). Two launches: (1) GN + q/k/v projection to token-major [n][N][8];
 // (2) attention + proj_out + residual + statistics of y for the next GroupNorm.
 #pragma once
+#include "attn_mfma.h"
 #include "unet_kernels.h"
 
 namespace gc {
@@ -151,12 +152,9 @@ __global__ __launch_bounds__(256) void attn_flash_kernel(const AttnFlashArgs a) 
 
 // The same attention on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 products and sums, like the lane-per-query form
 // above), flash style.  Workgroup = 64 queries x 4 key quarters = 8 waves (lanes l and l + 32 share a query); key / value tiles of 256 tokens in LDS ([key][9] and [key][33]: odd
-// strides, conflict-free operand reads; value columns 8 .. 31 stay zero so that V^T fills the 32 MFMA rows).  Per 32-key block:
-//   S^T[key][query] = K Q^T    4 MFMAs (8 channels = 4 k-pairs), A = K rows from LDS, B = Q from registers; a lane then owns ONE query
-//                              column and 16 of the 32 keys (the rest in lane ^ 32): softmax statistics are register-local + one exchange;
-//   O^T[d][query] += V^T P     16 MFMAs, A = V rows from LDS in the key order the P registers already have, B = P from the registers.
+// strides, conflict-free operand reads; value columns 8 .. 31 stay zero so that V^T fills the 32 MFMA rows).  Per 32-key block, on the
+// tile of attn_mfma.h: S^T[key][query] = K Q^T in 4 MFMAs (8 channels = 4 k-pairs), the running softmax, O^T[d][query] += V^T P in 16.
 // 2 agents x 2 048 tokens: 250 -> see DESIGN section 4 (the lane-per-query form keeps running maps below 128 tokens).
-using f32x16a = __attribute__((ext_vector_type(16))) float;
 __global__ __launch_bounds__(512) void attn_flash_mfma_kernel(const AttnFlashArgs a) {
   constexpr int KT = 256;
   __shared__ float sk[KT][9];
@@ -175,9 +173,8 @@ __global__ __launch_bounds__(512) void attn_flash_mfma_kernel(const AttnFlashArg
   float qv[4];
 #pragma unroll
   for (int s_ = 0; s_ < 4; ++s_) qv[s_] = ok ? a.Q[base + (size_t)i * 8 + 2 * s_ + h] : 0.f;
-  f32x16a o;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) o[r] = 0.f;
+  f32x16 o[1];   // O^T: the 8 channels are rows 0 .. 7 of one 32-row block
+  o[0] = mfma_zero();
   float mrun = -INFINITY, den = 0.f;
 
   for (int k0 = 0; k0 < a.HW; k0 += KT) {
@@ -197,37 +194,18 @@ __global__ __launch_bounds__(512) void attn_flash_mfma_kernel(const AttnFlashArg
     __syncthreads();
     const int nkb = (min(KT, a.HW - k0) + 31) / 32;
     for (int kb_ = 2 * kq; kb_ < min(nkb, 2 * kq + 2); ++kb_) {
-      f32x16a sc;
+      f32x16 sc = mfma_scores<8>(&sk[32 * kb_ + qi][h], qv);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) sc[r] = 0.f;
-#pragma unroll
-      for (int s_ = 0; s_ < 4; ++s_) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(sk[32 * kb_ + qi][2 * s_ + h], qv[s_], sc, 0, 0, 0);
-      float bm = -INFINITY;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = k0 + 32 * kb_ + 8 * (r >> 2) + 4 * h + (r & 3);
-        sc[r] = key < a.HW ? sc[r] : -INFINITY;
-        bm = fmaxf(bm, sc[r]);
-      }
-      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));   // every 32-key block holds at least one valid key: bm is finite
-      const float nm = fmaxf(mrun, bm), corr = __expf(mrun - nm);
-      float ps = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { sc[r] = __expf(sc[r] - nm); ps += sc[r]; }
-      den = den * corr + ps;
-      mrun = nm;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[r] *= corr;
-#pragma unroll
-      for (int t = 0; t < 16; ++t)
-        o = __builtin_amdgcn_mfma_f32_32x32x2f32(sv[32 * kb_ + 8 * (t >> 2) + 4 * h + (t & 3)][qi], sc[t], o, 0, 0, 0);
+      for (int r = 0; r < 16; ++r) sc[r] = mfma_row(r, h, k0 + 32 * kb_) < a.HW ? sc[r] : -INFINITY;
+      mfma_softmax_step<true>(sc, mrun, den, o);   // every 32-key block holds at least one valid key: the block maximum is finite
+      mfma_apply<1, 33>(&sv[0][qi], 32 * kb_, h, sc, o);
     }
   }
   den += __shfl_xor(den, 32, 64);
   // O^T rows 0 .. 7 are the channels: registers 0 .. 3 of a lane hold channels 4 h .. 4 h + 3 of its query
   if (h == 0) { s_partial[kq][ql][0] = mrun; s_partial[kq][ql][1] = den; }
 #pragma unroll
-  for (int c = 0; c < 4; ++c) s_partial[kq][ql][2 + 4 * h + c] = o[c];
+  for (int c = 0; c < 4; ++c) s_partial[kq][ql][2 + 4 * h + c] = o[0][c];
   __syncthreads();
   float part[16];
 #pragma unroll

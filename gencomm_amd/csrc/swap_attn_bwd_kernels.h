@@ -4,7 +4,7 @@
 //   D_i = sum_d dO_id O_id    dP_ij = dO_i . v_j    dS_ij = P_ij (dP_ij - D_i)
 //   dQ_i = scale sum_j dS_ij k_j    dK_j = scale sum_i dS_ij q_i    dV_j = sum_i P_ij dO_i    dtable[rel(i, j)][head] += dS_ij
 // Two passes, no T x T matrix in memory (320 x 320 per group and head at L 5, ws 8): each pass recomputes S on the fp32 matrix cores
-// (v_mfma_f32_32x32x2_f32) in the forward's arrangement, a wave owning 32 columns and a lane one column and 16 of the 32 rows:
+// (v_mfma_f32_32x32x2_f32) on the tile of attn_mfma.h, a wave owning 32 columns and a lane one column and 16 of the 32 rows:
 //   swap_attn_bwd_q_kernel   wave = 32 queries; K and V staged in tiles of 64 keys, the key loop ends at the last valid agent.
 //                            S^T = K Q^T and dP^T = V dO^T (A = rows from LDS, B = the wave's q / dO from registers), then
 //                            dQ^T[d][query] += K^T dS (A = K rows in the key order the dS registers have).  dS is also added into the
@@ -22,6 +22,8 @@
 
 namespace gc {
 
+#pragma clang fp contract(off)   // as in swap_attn_kernels.h
+
 struct SwapBwdArgs {
   const float* qkv;     // [B * L][3 * inner][H][W]
   const float* table;   // [(2 L - 1)(2 WS - 1)^2][heads]
@@ -37,29 +39,22 @@ struct SwapBwdArgs {
   float scale;
 };
 
+// The group a workgroup id is dealt (SwapBwdArgs::xcd): XCD k = blockIdx.x & 7 walks the k-th eighth of the groups.
+__device__ __forceinline__ int swap_bwd_bx(const SwapBwdArgs& a) {
+  return a.xcd ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+}
+
 template <int DH, int WS>
 __global__ __launch_bounds__(512) void swap_attn_bwd_q_kernel(const SwapBwdArgs a) {
   constexpr int T1 = WS * WS, KT = 64, DV = DH < 32 ? 32 : DH, LD = DV + 1, PW = 2 * WS - 1, PW2 = PW * PW;
-  constexpr int CH = DH < 32 ? DH : 32;
   extern __shared__ float swb_smem[];  // K [KT][LD], V [KT][LD] (columns DH .. 31 zero when DH < 32), bias and its gradient [(2 L - 1) PW2] each
-  const int L = a.L, NP = (2 * L - 1) * PW2;
+  const SwapGroup<DH, WS> g(a, a.nblk, swap_bwd_bx(a));
+  const int m = g.m, b = g.b, L = g.L, T = g.T, TV = g.TV, inner = g.inner, HW = g.HW, NP = (2 * L - 1) * PW2;
   float* sK = swb_smem;
   float* sV = sK + KT * LD;
   float* sP = sV + KT * LD;
   float* sD = sP + NP;
   const int tid = threadIdx.x, nthr = blockDim.x;
-  const int nchunk = (a.nblk + a.wpc - 1) / a.wpc;
-  const int bx = a.xcd ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
-  const int grp = bx / nchunk, chunk = bx - grp * nchunk;
-  const int m = blockIdx.y, b = blockIdx.z;
-  const int X = a.H / WS, Y = a.W / WS;
-  const int gx = grp / Y, gy = grp - gx * Y;
-  const int T = L * T1;
-  const int TV = min(max(a.nvalid[b], 1), L) * T1;
-  const int inner = a.heads * DH, HW = a.H * a.W;
-  const size_t agent = (size_t)3 * inner * HW;
-  const float* __restrict__ base = a.qkv + (size_t)b * L * agent;
-  auto pixel = [&](int w1, int w2) { return a.grid_mode ? (w1 * X + gx) * a.W + w2 * Y + gy : (gx * WS + w1) * a.W + gy * WS + w2; };
 
   for (int i = tid; i < NP; i += nthr) {
     sP[i] = a.table[(size_t)i * a.heads + m];
@@ -69,94 +64,54 @@ __global__ __launch_bounds__(512) void swap_attn_bwd_q_kernel(const SwapBwdArgs 
     for (int i = tid; i < 2 * KT * LD; i += nthr) sK[i] = 0.f;   // K and V: the columns beyond DH are never written again
 
   const int wave = tid >> 6, lane = tid & 63, qi = lane & 31, h = lane >> 5;
-  const int qb = chunk * a.wpc + wave;
+  const int qb = g.chunk * a.wpc + wave;
   const bool wave_live = wave < a.wpc && qb < a.nblk;
   const int qtok = qb * 32 + qi;
   const bool qok = wave_live && qtok < T;
   const int qt = qok ? qtok : 0;
   const int ql = qt / T1, qh = (qt % T1) / WS, qw = qt % WS;
-  const int qpix = pixel(qh, qw);
+  const int qpix = g.pixel(qh, qw);
   const size_t orow = ((size_t)(b * L + ql) * inner + m * DH) * HW + qpix;
   float qv[DH / 2], gv[DH / 2];
   float D = 0.f;
 #pragma unroll
   for (int s = 0; s < DH / 2; ++s) {
-    qv[s] = qok ? base[ql * agent + (size_t)(m * DH + 2 * s + h) * HW + qpix] * a.scale : 0.f;
+    qv[s] = qok ? g.base[ql * g.agent + (size_t)(m * DH + 2 * s + h) * HW + qpix] * a.scale : 0.f;
     gv[s] = qok ? a.dout[orow + (size_t)(2 * s + h) * HW] : 0.f;
     D = fmaf(gv[s], qok ? a.out[orow + (size_t)(2 * s + h) * HW] : 0.f, D);
   }
   D += __shfl_xor(D, 32, 64);
   const float lse = qok ? a.lse[((size_t)(b * L + ql) * a.heads + m) * HW + qpix] : 0.f;
-  f32x16s dq[DV / 32];
+  f32x16 dq[DV / 32];
 #pragma unroll
-  for (int db = 0; db < DV / 32; ++db)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) dq[db][i] = 0.f;
+  for (int db = 0; db < DV / 32; ++db) dq[db] = mfma_zero();
   const int pbase = (ql + L - 1) * PW2 + (qh + WS - 1) * PW + (qw + WS - 1);
 
   for (int k0 = 0; k0 < TV; k0 += KT) {
     __syncthreads();
-    for (int e = tid; e < 2 * KT; e += nthr) {
-      const int row = e & (KT - 1), isv = e / KT, key = k0 + row;
-      const bool live = key < TV;
-      const int kt = live ? key : 0;
-      const int kl = kt / T1, pix = pixel((kt % T1) / WS, kt % WS);
-      const float* __restrict__ src = base + kl * agent + (size_t)((1 + isv) * inner + m * DH) * HW + pix;
-      float* __restrict__ dst = (isv ? sV : sK) + row * LD;
-#pragma unroll
-      for (int c0 = 0; c0 < DH; c0 += CH) {
-        float v[CH];
-#pragma unroll
-        for (int c = 0; c < CH; ++c) v[c] = live ? src[(size_t)(c0 + c) * HW] : 0.f;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) dst[c0 + c] = v[c];
-      }
-    }
+    swap_fill_kv<DH, WS, LD, LD>(g, k0, sK, sV);
     __syncthreads();
     if (!wave_live) continue;
     const int nkb = (min(KT, TV - k0) + 31) >> 5;
 #pragma unroll 1
     for (int kb = 0; kb < nkb; ++kb) {
-      f32x16s sc, dp;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) sc[i] = dp[i] = 0.f;
-      const float* __restrict__ kr = sK + (32 * kb + qi) * LD + h;
-      const float* __restrict__ vr = sV + (32 * kb + qi) * LD + h;
-#pragma unroll
-      for (int s = 0; s < DH / 2; ++s) {   // two independent accumulators alternate
-        sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[2 * s], qv[s], sc, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[2 * s], gv[s], dp, 0, 0, 0);
-      }
+      const f32x16x2 sd = mfma_scores2<DH>(sK + (32 * kb + qi) * LD + h, qv, sV + (32 * kb + qi) * LD + h, gv);
+      f32x16 sc = sd.a, dp = sd.b;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int key = k0 + 32 * kb + 8 * (r >> 2) + 4 * h + (r & 3);
+        const int key = mfma_row(r, h, k0 + 32 * kb);
         const bool kok = qok && key < TV;
-        const int koff = (key / T1) * PW2 + ((key % T1) / WS) * PW + key % WS;
-        const int pi = kok ? pbase - koff : 0;
+        const int pi = kok ? pbase - g.rel_off(key) : 0;
         const float p = kok ? expf(sc[r] + sP[pi] - lse) : 0.f;
         const float ds = p * (dp[r] - D);
         sc[r] = ds;
         if (kok) atomicAdd(&sD[pi], ds);
       }
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        const int keyl = 32 * kb + 8 * (t >> 2) + 4 * h + (t & 3);
-#pragma unroll
-        for (int db = 0; db < DV / 32; ++db)
-          dq[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(sK[keyl * LD + 32 * db + qi], sc[t], dq[db], 0, 0, 0);
-      }
+      mfma_apply<DV / 32, LD>(sK + qi, 32 * kb, h, sc, dq);
     }
   }
-  if (qok) {
-    float* __restrict__ dqp = a.dqkv + (size_t)(b * L + ql) * agent + (size_t)(m * DH) * HW + qpix;
-#pragma unroll
-    for (int db = 0; db < DV / 32; ++db)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int ch = 32 * db + 8 * (r >> 2) + 4 * h + (r & 3);
-        if (DH >= 32 || (r >> 2) < DH / 8) dqp[(size_t)ch * HW] = dq[db][r] * a.scale;
-      }
-  }
+  if (qok)
+    mfma_store_t<DH>(a.dqkv + (size_t)(b * L + ql) * g.agent + (size_t)(m * DH) * HW + qpix, HW, h, dq, [&](float x) { return x * a.scale; });
   __syncthreads();
   for (int i = tid; i < NP; i += nthr)
     if (sD[i] != 0.f) atomicAdd(&a.dtable[(size_t)i * a.heads + m], sD[i]);
@@ -167,25 +122,14 @@ __global__ __launch_bounds__(512) void swap_attn_bwd_k_kernel(const SwapBwdArgs 
   constexpr int T1 = WS * WS, QT = 64, DV = DH < 32 ? 32 : DH, LD = DV + 1, PW = 2 * WS - 1, PW2 = PW * PW;
   constexpr int CH = DH < 32 ? DH : 32;
   extern __shared__ float swb_smem[];  // Q scaled [QT][LD], dO [QT][LD] (columns DH .. 31 zero when DH < 32), lse [QT], D [QT], bias [(2 L - 1) PW2]
-  const int L = a.L, NP = (2 * L - 1) * PW2;
+  const SwapGroup<DH, WS> g(a, a.nblk, swap_bwd_bx(a));
+  const int m = g.m, b = g.b, L = g.L, T = g.T, TV = g.TV, inner = g.inner, HW = g.HW, NP = (2 * L - 1) * PW2;
   float* sQ = swb_smem;
   float* sG = sQ + QT * LD;
   float* sL = sG + QT * LD;
   float* sDd = sL + QT;
   float* sP = sDd + QT;
   const int tid = threadIdx.x, nthr = blockDim.x;
-  const int nchunk = (a.nblk + a.wpc - 1) / a.wpc;
-  const int bx = a.xcd ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
-  const int grp = bx / nchunk, chunk = bx - grp * nchunk;
-  const int m = blockIdx.y, b = blockIdx.z;
-  const int X = a.H / WS, Y = a.W / WS;
-  const int gx = grp / Y, gy = grp - gx * Y;
-  const int T = L * T1;
-  const int TV = min(max(a.nvalid[b], 1), L) * T1;
-  const int inner = a.heads * DH, HW = a.H * a.W;
-  const size_t agent = (size_t)3 * inner * HW;
-  const float* __restrict__ base = a.qkv + (size_t)b * L * agent;
-  auto pixel = [&](int w1, int w2) { return a.grid_mode ? (w1 * X + gx) * a.W + w2 * Y + gy : (gx * WS + w1) * a.W + gy * WS + w2; };
 
   for (int i = tid; i < NP; i += nthr) sP[i] = a.table[(size_t)i * a.heads + m];
   if (DV != DH)
@@ -193,7 +137,7 @@ __global__ __launch_bounds__(512) void swap_attn_bwd_k_kernel(const SwapBwdArgs 
 
   // wave = one block of 32 keys (lanes l and l + 32 share a key)
   const int wave = tid >> 6, lane = tid & 63, qi = lane & 31, h = lane >> 5;
-  const int kb = chunk * a.wpc + wave;
+  const int kb = g.chunk * a.wpc + wave;
   const bool wave_live = wave < a.wpc && kb < a.nblk;
   const int ktok = kb * 32 + qi;
   const bool kok = wave_live && ktok < T;          // a key of the group: its dK and dV rows are stored here
@@ -201,21 +145,22 @@ __global__ __launch_bounds__(512) void swap_attn_bwd_k_kernel(const SwapBwdArgs 
   const bool wave_work = wave_live && kb * 32 < TV;   // wave-uniform: the block's first key is valid
   const int kt = kok ? ktok : 0;
   const int kl = kt / T1, kh = (kt % T1) / WS, kw = kt % WS;
-  const int kpix = pixel(kh, kw);
+  const int kpix = g.pixel(kh, kw);
   float kv[DH / 2], vv[DH / 2];
 #pragma unroll
   for (int s = 0; s < DH / 2; ++s) {
-    kv[s] = kvalid ? base[kl * agent + (size_t)(inner + m * DH + 2 * s + h) * HW + kpix] : 0.f;
-    vv[s] = kvalid ? base[kl * agent + (size_t)(2 * inner + m * DH + 2 * s + h) * HW + kpix] : 0.f;
+    kv[s] = kvalid ? g.base[kl * g.agent + (size_t)(inner + m * DH + 2 * s + h) * HW + kpix] : 0.f;
+    vv[s] = kvalid ? g.base[kl * g.agent + (size_t)(2 * inner + m * DH + 2 * s + h) * HW + kpix] : 0.f;
   }
-  f32x16s dk[DV / 32], dv[DV / 32];
+  f32x16 dk[DV / 32], dv[DV / 32];
 #pragma unroll
-  for (int db = 0; db < DV / 32; ++db)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) dk[db][i] = dv[db][i] = 0.f;
-  // rel(query, key) = qoff(query) + pk with pk = (L - 1 - kl) PW2 + (WS - 1 - kh) PW + (WS - 1 - kw)
+  for (int db = 0; db < DV / 32; ++db) {
+    dk[db] = mfma_zero();
+    dv[db] = mfma_zero();
+  }
+  // rel(query, key) = off(query) + pk with pk = (L - 1 - kl) PW2 + (WS - 1 - kh) PW + (WS - 1 - kw)
   const int pk = (L - 1 - kl) * PW2 + (WS - 1 - kh) * PW + (WS - 1 - kw);
-  const int qend = chunk * a.wpc * 32 < TV ? T : 0;   // a workgroup whose keys are all masked stages nothing
+  const int qend = g.chunk * a.wpc * 32 < TV ? T : 0;   // a workgroup whose keys are all masked stages nothing
 
   for (int q0 = 0; q0 < qend; q0 += QT) {
     __syncthreads();
@@ -223,20 +168,12 @@ __global__ __launch_bounds__(512) void swap_attn_bwd_k_kernel(const SwapBwdArgs 
       const int row = e & (QT - 1), isg = e / QT, tok = q0 + row;
       const bool live = tok < T;
       const int t = live ? tok : 0;
-      const int tl = t / T1, pix = pixel((t % T1) / WS, t % WS);
+      const int tl = t / T1, pix = g.pixel((t % T1) / WS, t % WS);
       if (!isg) {
-        const float* __restrict__ src = base + tl * agent + (size_t)(m * DH) * HW + pix;
-        float* __restrict__ dst = sQ + row * LD;
-#pragma unroll
-        for (int c0 = 0; c0 < DH; c0 += CH) {
-          float v[CH];
-#pragma unroll
-          for (int c = 0; c < CH; ++c) v[c] = live ? src[(size_t)(c0 + c) * HW] * a.scale : 0.f;
-#pragma unroll
-          for (int c = 0; c < CH; ++c) dst[c0 + c] = v[c];
-        }
+        const float* __restrict__ src = g.base + tl * g.agent + (size_t)(m * DH) * HW + pix;
+        swap_fill_row<DH>(sQ + row * LD, live, [&](int c) { return src[(size_t)c * HW] * a.scale; });
         sL[row] = live ? a.lse[((size_t)(b * L + tl) * a.heads + m) * HW + pix] : 0.f;
-      } else {
+      } else {   // the dO row also sums D = dO . O, channel by channel as it is staged
         const size_t off = ((size_t)(b * L + tl) * inner + m * DH) * HW + pix;
         float* __restrict__ dst = sG + row * LD;
         float dsum = 0.f;
@@ -262,58 +199,32 @@ __global__ __launch_bounds__(512) void swap_attn_bwd_k_kernel(const SwapBwdArgs 
     const int nqb = (min(QT, T - q0) + 31) >> 5;
 #pragma unroll 1
     for (int qb = 0; qb < nqb; ++qb) {
-      f32x16s sc, dp;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) sc[i] = dp[i] = 0.f;
-      const float* __restrict__ qr = sQ + (32 * qb + qi) * LD + h;
-      const float* __restrict__ gr = sG + (32 * qb + qi) * LD + h;
-#pragma unroll
-      for (int s = 0; s < DH / 2; ++s) {
-        sc = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[2 * s], kv[s], sc, 0, 0, 0);   // S[query][key]: a lane owns one key column
-        dp = __builtin_amdgcn_mfma_f32_32x32x2f32(gr[2 * s], vv[s], dp, 0, 0, 0);
-      }
+      // S[query][key] and dP: a lane owns one key column
+      const f32x16x2 sd = mfma_scores2<DH>(sQ + (32 * qb + qi) * LD + h, kv, sG + (32 * qb + qi) * LD + h, vv);
+      f32x16 sc = sd.a, dp = sd.b;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int rowl = 32 * qb + 8 * (r >> 2) + 4 * h + (r & 3), tok = q0 + rowl;
+        const int rowl = mfma_row(r, h, 32 * qb), tok = q0 + rowl;
         const bool ok = kvalid && tok < T;
-        const int qoff = (tok / T1) * PW2 + ((tok % T1) / WS) * PW + tok % WS;
-        const float p = ok ? expf(sc[r] + sP[ok ? qoff + pk : 0] - sL[rowl]) : 0.f;
+        const float p = ok ? expf(sc[r] + sP[ok ? g.rel_off(tok) + pk : 0] - sL[rowl]) : 0.f;
         sc[r] = p;
         dp[r] = p * (dp[r] - sDd[rowl]);
       }
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        const int rowl = 32 * qb + 8 * (t >> 2) + 4 * h + (t & 3);
-#pragma unroll
-        for (int db = 0; db < DV / 32; ++db) {
-          dv[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(sG[rowl * LD + 32 * db + qi], sc[t], dv[db], 0, 0, 0);
-          dk[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(sQ[rowl * LD + 32 * db + qi], dp[t], dk[db], 0, 0, 0);
-        }
-      }
+      mfma_apply2<DV / 32, LD>(sG + qi, sQ + qi, 32 * qb, h, sc, dp, dv, dk);
     }
   }
   if (!kok) return;   // no barrier follows
-  float* __restrict__ dkp = a.dqkv + (size_t)(b * L + kl) * agent + (size_t)(inner + m * DH) * HW + kpix;
-  float* __restrict__ dvp = dkp + (size_t)inner * HW;
-#pragma unroll
-  for (int db = 0; db < DV / 32; ++db)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int ch = 32 * db + 8 * (r >> 2) + 4 * h + (r & 3);
-      if (DH >= 32 || (r >> 2) < DH / 8) {
-        dkp[(size_t)ch * HW] = kvalid ? dk[db][r] : 0.f;   // exact zeros for the keys of masked agents
-        dvp[(size_t)ch * HW] = kvalid ? dv[db][r] : 0.f;
-      }
-    }
+  float* __restrict__ dkp = a.dqkv + (size_t)(b * L + kl) * g.agent + (size_t)(inner + m * DH) * HW + kpix;
+  auto keep = [&](float x) { return kvalid ? x : 0.f; };   // exact zeros for the keys of masked agents
+  mfma_store_t<DH>(dkp, HW, h, dk, keep);
+  mfma_store_t<DH>(dkp + (size_t)inner * HW, HW, h, dv, keep);
 }
 
 template <int DH, int WS>
 inline int swap_attn_bwd_launch(SwapBwdArgs a, int B, hipStream_t st) {
   constexpr int DV = DH < 32 ? 32 : DH, PW = 2 * WS - 1;
-  a.nblk = (a.L * WS * WS + 31) / 32;
-  const int split = (a.nblk + 7) / 8;
-  a.wpc = (a.nblk + split - 1) / split;
-  const int nchunk = (a.nblk + a.wpc - 1) / a.wpc;
+  int nchunk;
+  swap_split(a.L, WS, a.nblk, a.wpc, nchunk);
   const size_t np = (size_t)(2 * a.L - 1) * PW * PW;
   const size_t shm_q = ((size_t)2 * 64 * (DV + 1) + 2 * np) * sizeof(float);
   const size_t shm_k = ((size_t)2 * 64 * (DV + 1) + 2 * 64 + np) * sizeof(float);
@@ -336,5 +247,7 @@ inline int swap_attn_bwd_launch(SwapBwdArgs a, int B, hipStream_t st) {
   GC_HIP(hipGetLastError());
   return GC_OK;
 }
+
+#pragma clang fp contract(fast)
 
 }  // namespace gc

@@ -14,10 +14,7 @@
 // final mean over all L agents; only their KEYS are masked.  The ego (agent 0) is always valid, so no row is fully masked.
 //
 // fp32 in, out and accumulation on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 products, an fmaf chain), in the
-// arrangement of win_attn_mfma_kernel: a wave owns one block of 32 queries and walks the keys in blocks of 32,
-//   S^T[key][query] = K Q^T   A = K rows from LDS, B = Q (scaled) from registers; a lane then owns ONE query column and 16 of the 32
-//                             keys (the others in lane ^ 32): softmax statistics are register-local plus one exchange;
-//   O^T[d][query] += V^T P    A = V rows from LDS in the key order the P registers already have, B = P from the registers.
+// tile of attn_mfma.h: a wave owns one block of 32 queries and walks the keys in blocks of 32, S^T[key][query] = K Q^T, O^T += V^T P.
 // 320 tokens (L 5, ws 8) x dim_head 64 of K and V are 166 KB: the keys are staged in tiles of 64 ([key][DH + 1] rows: odd stride,
 // conflict-free fills and operand reads) with a running softmax.  64 keys are four agents of a 4 x 4 group or one agent of an 8 x 8
 // group, so the key loop ends at the last VALID agent: masked agents cost nothing at ws 8 and at most part of one tile at ws 4.
@@ -26,9 +23,13 @@
 // swap_attn_kernel<DH, WS, true> (gencomm_swap_attn_train_fwd) is the same body with one more store per query, lse = running max +
 // log(running denominator), which swap_attn_bwd_kernels.h turns back into the probabilities; `out` is computed by the same instructions.
 #pragma once
-#include "common.h"
+#include "attn_mfma.h"
 
 namespace gc {
+
+// Contraction is off for everything in this header and in swap_attn_bwd_kernels.h: a product and the sum it feeds are rounded one after
+// the other, wherever the header is included.
+#pragma clang fp contract(off)
 
 constexpr int kSwapMaxAgents = 8;  // MAX_AGENTS_PER_SCENE of the Python package
 
@@ -43,30 +44,74 @@ struct SwapArgs {
   float* lse;           // [B * L][heads][H][W], written by the TRAIN instantiation only: running max + log(running denominator)
 };
 
-using f32x16s = __attribute__((ext_vector_type(16))) float;
+// The (group, head, scene) of a workgroup and where its tokens live, for the forward and both backward kernels (Args = SwapArgs or
+// SwapBwdArgs).  bx = blockIdx.x, or the backward's remap of it (swap_bwd_bx); nblk = blocks of 32 tokens per group.
+template <int DH, int WS>
+struct SwapGroup {
+  static constexpr int T1 = WS * WS, PW = 2 * WS - 1, PW2 = PW * PW;
+  int chunk, m, b, L, T, TV, inner, HW, W, X, Y, gx, gy, grid_mode;
+  size_t agent;                     // floats of one agent's q | k | v
+  const float* __restrict__ base;   // the scene's qkv
+  template <class Args>
+  __device__ __forceinline__ SwapGroup(const Args& a, int nblk, int bx) {
+    const int nchunk = (nblk + a.wpc - 1) / a.wpc, grp = bx / nchunk;
+    chunk = bx - grp * nchunk;
+    m = blockIdx.y, b = blockIdx.z, L = a.L, W = a.W, grid_mode = a.grid_mode;
+    X = a.H / WS, Y = a.W / WS;
+    gx = grp / Y, gy = grp - gx * Y;
+    T = L * T1;                                       // tokens = queries of the group
+    TV = min(max(a.nvalid[b], 1), L) * T1;            // its valid keys: the agents present come first
+    inner = a.heads * DH, HW = a.H * a.W;
+    agent = (size_t)3 * inner * HW;
+    base = a.qkv + (size_t)b * L * agent;
+  }
+  // pixel of the token's (w1, w2) inside this group
+  __device__ __forceinline__ int pixel(int w1, int w2) const {
+    return grid_mode ? (w1 * X + gx) * W + w2 * Y + gy : (gx * WS + w1) * W + gy * WS + w2;
+  }
+  // offset of token (l, w1, w2) in the relative position table: rel(query, key) = off(query) - off(key) + the centre
+  // (L - 1) PW2 + (WS - 1) PW + WS - 1
+  static __device__ __forceinline__ int rel_off(int tok) { return (tok / T1) * PW2 + ((tok % T1) / WS) * PW + tok % WS; }
+};
+
+// One row of a staged tile: DH channels through registers, up to 32 loads in flight before the first LDS store; a dead row becomes zeros.
+template <int DH, class Load>
+__device__ __forceinline__ void swap_fill_row(float* dst, bool live, Load load) {
+  constexpr int CH = DH < 32 ? DH : 32;   // channels a fill thread has in flight
+#pragma unroll
+  for (int c0 = 0; c0 < DH; c0 += CH) {
+    float v[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) v[c] = live ? load(c0 + c) : 0.f;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) dst[c0 + c] = v[c];
+  }
+}
+
+// The K | V tile of keys k0 .. k0 + 63 of head g.m: one (key, K or V) row per thread and pass; keys beyond the valid ones become zero rows.
+template <int DH, int WS, int LDK, int LDV>
+__device__ __forceinline__ void swap_fill_kv(const SwapGroup<DH, WS>& g, int k0, float* sK, float* sV) {
+  constexpr int KT = 64, T1 = WS * WS;
+  for (int e = threadIdx.x; e < 2 * KT; e += blockDim.x) {
+    const int row = e & (KT - 1), isv = e / KT, key = k0 + row;
+    const bool live = key < g.TV;
+    const int kt = live ? key : 0;
+    const float* __restrict__ src = g.base + (kt / T1) * g.agent + (size_t)((1 + isv) * g.inner + g.m * DH) * g.HW + g.pixel((kt % T1) / WS, kt % WS);
+    swap_fill_row<DH>(isv ? sV + row * LDV : sK + row * LDK, live, [&](int c) { return src[(size_t)c * g.HW]; });
+  }
+}
 
 template <int DH, int WS, bool TRAIN = false>
 __global__ __launch_bounds__(512) void swap_attn_kernel(const SwapArgs a) {
   constexpr int T1 = WS * WS, KT = 64, LDK = DH + 1, DV = DH < 32 ? 32 : DH, LDV = DV + 1, PW = 2 * WS - 1, PW2 = PW * PW;
-  constexpr int CH = DH < 32 ? DH : 32;   // channels a fill thread has in flight
   static_assert(KT % T1 == 0 && DH % 16 == 0 && DH <= 64, "4 x 4 or 8 x 8 groups, head width 16, 32 or 64");
   extern __shared__ float sw_smem[];  // K [KT][LDK], V [KT][LDV] (columns DH .. 31 zero when DH < 32), bias of this head [(2 L - 1) PW2]
   float* sK = sw_smem;
   float* sV = sK + KT * LDK;
   float* sP = sV + KT * LDV;
   const int tid = threadIdx.x, nthr = blockDim.x;
-  const int nchunk = (a.nqb + a.wpc - 1) / a.wpc;
-  const int grp = blockIdx.x / nchunk, chunk = blockIdx.x - grp * nchunk;
-  const int m = blockIdx.y, b = blockIdx.z;
-  const int X = a.H / WS, Y = a.W / WS, L = a.L;
-  const int gx = grp / Y, gy = grp - gx * Y;
-  const int T = L * T1;                                   // tokens = queries of the group
-  const int TV = min(max(a.nvalid[b], 1), L) * T1;        // its valid keys: the agents present come first
-  const int inner = a.heads * DH, HW = a.H * a.W;
-  const size_t agent = (size_t)3 * inner * HW;
-  const float* __restrict__ base = a.qkv + (size_t)b * L * agent;
-  // pixel of the token's (w1, w2) inside this group
-  auto pixel = [&](int w1, int w2) { return a.grid_mode ? (w1 * X + gx) * a.W + w2 * Y + gy : (gx * WS + w1) * a.W + gy * WS + w2; };
+  const SwapGroup<DH, WS> g(a, a.nqb, blockIdx.x);
+  const int m = g.m, b = g.b, L = g.L, T = g.T, TV = g.TV, inner = g.inner, HW = g.HW;
 
   for (int i = tid; i < (2 * L - 1) * PW2; i += nthr) sP[i] = a.table[(size_t)i * a.heads + m];
   if (DV != DH)
@@ -74,95 +119,55 @@ __global__ __launch_bounds__(512) void swap_attn_kernel(const SwapArgs a) {
 
   // wave = one block of 32 queries (lanes l and l + 32 share a query)
   const int wave = tid >> 6, lane = tid & 63, qi = lane & 31, h = lane >> 5;
-  const int qb = chunk * a.wpc + wave;
+  const int qb = g.chunk * a.wpc + wave;
   const bool wave_live = wave < a.wpc && qb < a.nqb;      // wave-uniform; a wave without queries still fills and meets the barriers
   const int qtok = qb * 32 + qi;
   const bool qok = wave_live && qtok < T;
   const int qt = qok ? qtok : 0;
   const int ql = qt / T1, qh = (qt % T1) / WS, qw = qt % WS;
-  const int qpix = pixel(qh, qw);
+  const int qpix = g.pixel(qh, qw);
   float qv[DH / 2];
 #pragma unroll
-  for (int s = 0; s < DH / 2; ++s) qv[s] = qok ? base[ql * agent + (size_t)(m * DH + 2 * s + h) * HW + qpix] * a.scale : 0.f;
-  f32x16s o[DV / 32];
+  for (int s = 0; s < DH / 2; ++s) qv[s] = qok ? g.base[ql * g.agent + (size_t)(m * DH + 2 * s + h) * HW + qpix] * a.scale : 0.f;
+  f32x16 o[DV / 32];
 #pragma unroll
-  for (int db = 0; db < DV / 32; ++db)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) o[db][i] = 0.f;
+  for (int db = 0; db < DV / 32; ++db) o[db] = mfma_zero();
   float mrun = -INFINITY, den = 0.f;
   const int pbase = (ql + L - 1) * PW2 + (qh + WS - 1) * PW + (qw + WS - 1);
 
   for (int k0 = 0; k0 < TV; k0 += KT) {
     __syncthreads();   // the previous tile is no longer read (first pass: the bias and the zero fill are complete after the next one)
-    for (int e = tid; e < 2 * KT; e += nthr) {   // one (key, K or V) row per pass; keys beyond the valid ones become zero rows
-      const int row = e & (KT - 1), isv = e / KT, key = k0 + row;
-      const bool live = key < TV;
-      const int kt = live ? key : 0;
-      const int kl = kt / T1, pix = pixel((kt % T1) / WS, kt % WS);
-      const float* __restrict__ src = base + kl * agent + (size_t)((1 + isv) * inner + m * DH) * HW + pix;
-      float* __restrict__ dst = isv ? sV + row * LDV : sK + row * LDK;
-#pragma unroll
-      for (int c0 = 0; c0 < DH; c0 += CH) {
-        float v[CH];
-#pragma unroll
-        for (int c = 0; c < CH; ++c) v[c] = live ? src[(size_t)(c0 + c) * HW] : 0.f;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) dst[c0 + c] = v[c];
-      }
-    }
+    swap_fill_kv<DH, WS, LDK, LDV>(g, k0, sK, sV);
     __syncthreads();
     if (!wave_live) continue;
     const int nkb = (min(KT, TV - k0) + 31) >> 5;   // every walked block of 32 begins with a valid key
 #pragma unroll 1
     for (int kb = 0; kb < nkb; ++kb) {
-      f32x16s sc;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) sc[i] = 0.f;
-      const float* __restrict__ kr = sK + (32 * kb + qi) * LDK + h;
-#pragma unroll
-      for (int s = 0; s < DH / 2; ++s) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[2 * s], qv[s], sc, 0, 0, 0);
-      float bm = -INFINITY;
+      f32x16 sc = mfma_scores<DH>(sK + (32 * kb + qi) * LDK + h, qv);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int key = k0 + 32 * kb + 8 * (r >> 2) + 4 * h + (r & 3);
+        const int key = mfma_row(r, h, k0 + 32 * kb);
         const bool kok = key < TV;
-        const int koff = (key / T1) * PW2 + ((key % T1) / WS) * PW + key % WS;   // rel(query, key) = pbase - koff
-        const float bias = sP[kok ? pbase - koff : 0];
+        const float bias = sP[kok ? pbase - g.rel_off(key) : 0];   // rel(query, key) = pbase - off(key)
         sc[r] = kok ? sc[r] + bias : -INFINITY;
-        bm = fmaxf(bm, sc[r]);
       }
-      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));   // finite: the block's first key is valid
-      const float nm = fmaxf(mrun, bm), corr = expf(mrun - nm);
-      float ps = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { sc[r] = expf(sc[r] - nm); ps += sc[r]; }
-      den = den * corr + ps;
-      mrun = nm;
-#pragma unroll
-      for (int db = 0; db < DV / 32; ++db)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[db][i] *= corr;
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        const int keyl = 32 * kb + 8 * (t >> 2) + 4 * h + (t & 3);
-#pragma unroll
-        for (int db = 0; db < DV / 32; ++db)  // the head's 32-wide halves alternate: consecutive MFMAs never share an accumulator
-          o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(sV[keyl * LDV + 32 * db + qi], sc[t], o[db], 0, 0, 0);
-      }
+      mfma_softmax_step<false>(sc, mrun, den, o);   // finite: the block's first key is valid
+      mfma_apply<DV / 32, LDV>(sV + qi, 32 * kb, h, sc, o);
     }
   }
   if (!qok) return;   // no barrier follows
   den += __shfl_xor(den, 32, 64);   // the partner lane holds the same query: it is live too
   const float rden = 1.0f / den;
-  float* __restrict__ op = a.out + ((size_t)(b * L + ql) * inner + m * DH) * HW + qpix;
-#pragma unroll
-  for (int db = 0; db < DV / 32; ++db)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int ch = 32 * db + 8 * (r >> 2) + 4 * h + (r & 3);
-      if (DH >= 32 || (r >> 2) < DH / 8) op[(size_t)ch * HW] = o[db][r] * rden;
-    }
+  mfma_store_t<DH>(a.out + ((size_t)(b * L + ql) * inner + m * DH) * HW + qpix, HW, h, o, [&](float x) { return x * rden; });
   if (TRAIN && h == 0) a.lse[((size_t)(b * L + ql) * a.heads + m) * HW + qpix] = mrun + logf(den);
+}
+
+// The split of a group's blocks of 32 tokens over workgroups: at most 8 blocks (= waves) each, evenly.
+inline void swap_split(int L, int ws, int& nblk, int& wpc, int& nchunk) {
+  nblk = (L * ws * ws + 31) / 32;
+  const int split = (nblk + 7) / 8;
+  wpc = (nblk + split - 1) / split;
+  nchunk = (nblk + wpc - 1) / wpc;
 }
 
 inline void swap_attn_klog(int dh, int ws, const char* kernel = "swap_attn_kernel", const char* tail = "") {
@@ -175,10 +180,8 @@ inline void swap_attn_klog(int dh, int ws, const char* kernel = "swap_attn_kerne
 template <int DH, int WS, bool TRAIN = false>
 inline int swap_attn_launch(SwapArgs a, int B, hipStream_t st) {
   constexpr int DV = DH < 32 ? 32 : DH, PW = 2 * WS - 1;
-  a.nqb = (a.L * WS * WS + 31) / 32;
-  const int split = (a.nqb + 7) / 8;            // workgroups per group: at most 8 query blocks each, evenly
-  a.wpc = (a.nqb + split - 1) / split;
-  const int nchunk = (a.nqb + a.wpc - 1) / a.wpc;
+  int nchunk;
+  swap_split(a.L, WS, a.nqb, a.wpc, nchunk);
   const size_t shm = ((size_t)64 * (DH + 1) + 64 * (DV + 1) + (2 * a.L - 1) * PW * PW) * sizeof(float);
   if (shm > 48 * 1024)
     GC_HIP(hipFuncSetAttribute((const void*)swap_attn_kernel<DH, WS, TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
@@ -209,5 +212,7 @@ __global__ __launch_bounds__(256) void agent_mean_kernel(const float* __restrict
   for (int l = 0; l < L; ++l) s += p[(size_t)l * count];
   out[(size_t)blockIdx.y * count + i] = s / (float)L;
 }
+
+#pragma clang fp contract(fast)
 
 }  // namespace gc

@@ -10,8 +10,10 @@
 //                        plain masked softmax attention over at most 8 agents here.
 //   win_attn_kernel      BaseWindowAttention's core (mswin.py:47-83): per agent, head and window, softmax(q k^T scale +
 //                        relative position bias) v with the keys / values of the window staged in LDS.
-// fp32 throughout; softmax with the running maximum; one lane per query.
+// fp32 throughout; softmax with the running maximum; one lane per query, except win_attn_mfma_kernel (windows of 64 or 256 tokens),
+// which runs on the matrix-core tile of attn_mfma.h.
 #pragma once
+#include "attn_mfma.h"
 #include "common.h"
 #include "fuse_cell.h"
 
@@ -223,14 +225,9 @@ __global__ __launch_bounds__(256) void win_attn_kernel(const WinArgs a) {
 // The same attention on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 products and sums, as the lane-per-query form)
 // for windows of 64 or 256 tokens.  Workgroup = 256 tokens (one 16x16 window or four 8x8 windows) of one head; its keys and values
 // sit in LDS as [token][DH + 1] rows (odd stride: conflict-free fills and operand reads).  8 waves: a wave owns one block of 32 queries (two
-// waves per SIMD, so one wave's softmax arithmetic runs under the other's MFMAs) and walks its window's keys in blocks of 32, flash style:
-//   S^T[key][query] = K Q^T   A = K rows from LDS, B = Q (scaled) from registers (DH / 2 MFMAs); the block comes out with a lane owning
-//                             ONE query column and 16 of the 32 keys (the other 16 in lane ^ 32), so the softmax statistics are
-//                             register-local plus one exchange;
-//   + relative position bias, running max / denominator, P = exp(S - max);
-//   O^T[d][query] += V^T P    A = V rows from LDS in the key order the P registers already have, B = P straight from the registers.
+// waves per SIMD, so one wave's softmax arithmetic runs under the other's MFMAs) and walks its window's keys in blocks of 32, flash style,
+// on the tile of attn_mfma.h: S^T[key][query] = K Q^T, + relative position bias, the running softmax, O^T[d][query] += V^T P.
 // 64 MFMAs per 32 x 32 block at DH = 64 against 8 k broadcast LDS reads + 4 k FMAs per lane in the form above.
-using f32x16w = __attribute__((ext_vector_type(16))) float;
 template <int DH, int WS>
 __global__ __launch_bounds__(512) void win_attn_mfma_kernel(const WinArgs a) {
   constexpr int T = WS * WS, WPB = 256 / T, LD = DH + 1, NKB = T / 32, PW = 2 * WS - 1;
@@ -275,54 +272,25 @@ __global__ __launch_bounds__(512) void win_attn_mfma_kernel(const WinArgs a) {
   float qv[DH / 2];
 #pragma unroll
   for (int s = 0; s < DH / 2; ++s) qv[s] = base[(size_t)(m * DH + 2 * s + h) * HW + qpix] * a.scale;
-  f32x16w o[DH / 32];
+  f32x16 o[DH / 32];
 #pragma unroll
-  for (int db = 0; db < DH / 32; ++db)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) o[db][i] = 0.f;
+  for (int db = 0; db < DH / 32; ++db) o[db] = mfma_zero();
   float mrun = -INFINITY, den = 0.f;
   const int pbase = (WS - 1 - qy) * PW + (WS - 1 - qx);
 #pragma unroll 1
   for (int kb = 0; kb < NKB; ++kb) {
-    f32x16w sc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) sc[i] = 0.f;
-    const float* __restrict__ kr = kw + (32 * kb + qi) * LD + h;
-#pragma unroll
-    for (int s = 0; s < DH / 2; ++s) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[2 * s], qv[s], sc, 0, 0, 0);
-    float bm = -INFINITY;
+    f32x16 sc = mfma_scores<DH>(kw + (32 * kb + qi) * LD + h, qv);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int key = 32 * kb + 8 * (r >> 2) + 4 * h + (r & 3);
+      const int key = mfma_row(r, h, 32 * kb);
       sc[r] += sP[pbase + (key / WS) * PW + key % WS];  // relative_indices[query][key] = idx[key] - idx[query] + WS - 1 (mswin.py:12-16, :34-35)
-      bm = fmaxf(bm, sc[r]);
     }
-    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-    const float nm = fmaxf(mrun, bm), corr = __expf(mrun - nm);
-    float ps = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { sc[r] = __expf(sc[r] - nm); ps += sc[r]; }
-    den = den * corr + ps;
-    mrun = nm;
-#pragma unroll
-    for (int db = 0; db < DH / 32; ++db)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) o[db][i] *= corr;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const int key = 32 * kb + 8 * (t >> 2) + 4 * h + (t & 3);
-#pragma unroll
-      for (int db = 0; db < DH / 32; ++db)  // the head's 32-wide halves alternate: consecutive MFMAs never share an accumulator
-        o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(vw[key * LD + 32 * db + qi], sc[t], o[db], 0, 0, 0);
-    }
+    mfma_softmax_step<true>(sc, mrun, den, o);
+    mfma_apply<DH / 32, LD>(vw + qi, 32 * kb, h, sc, o);
   }
   den += __shfl_xor(den, 32, 64);
   const float rden = 1.0f / den;
-  float* __restrict__ op = a.out + ((size_t)n * inner + m * DH) * HW + qpix;
-#pragma unroll
-  for (int db = 0; db < DH / 32; ++db)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) op[(size_t)(32 * db + 8 * (r >> 2) + 4 * h + (r & 3)) * HW] = o[db][r] * rden;
+  mfma_store_t<DH>(a.out + ((size_t)n * inner + m * DH) * HW + qpix, HW, h, o, [&](float x) { return x * rden; });
 }
 
 // kernel log (gencomm_klog_start / _stop): which of the two forms a (window, dim_head) pair went to

@@ -3,7 +3,8 @@ operation in float64 (tests/v2xvit_kernel_reference.py):
 
   window attention  gencomm_win_attn_fwd / _bwd: all seven (window, dim_head) pairs -- win_attn_mfma_kernel for (8,32) (8,64) (16,32)
                     (16,64), win_attn_kernel for (4,16) (4,32) (8,16); the form that ran is read from the kernel log -- on a map whose
-                    window count fills every workgroup and on one whose last workgroup is partly filled, at unit and at large logits
+                    window count fills every workgroup and on one whose last workgroup is partly filled, at unit and at large logits;
+                    and against gencomm_swap_attn_fwd where CoBEVT's swap attention is the same function (one agent, window partition)
   agent attention   gencomm_hgt_attn_fwd at dim_head 8 .. 64 with scenes of 1 .. 8 agents in one launch, per-query-agent and streaming
                     form; gencomm_hgt_attn_bwd at dim_head 8, 16, 64
   warp              gencomm_warp_affine_fwd / _bwd: identity, whole-pixel shift, rotation, sampling positions within a pixel of each
@@ -179,6 +180,42 @@ def test_win_attn_bwd(ws, dh, which, scale):
         assert diff <= bound
     finally:
         rep.show()
+
+
+@pytest.mark.parametrize("ws,dh", [(8, 32), (8, 64), (4, 32)])
+def test_swap_and_window_attention_agree_where_they_overlap(ws, dh):
+    """CoBEVT's swap attention with one agent per scene and the window partition is plain window attention, so gencomm_swap_attn_fwd
+    and gencomm_win_attn_fwd must agree there: (8, 32) and (8, 64) run the matrix-core tile (csrc/attn_mfma.h) on both sides, (4, 32)
+    the lane-per-query kernel on the window side.  The swap table is indexed by query - key and pos by key - query, so table[i][head] =
+    pos.flatten()[(2 ws - 1)^2 - 1 - i].  Map 16 x 24 (X != Y), two heads, two scenes, qkv as in test_swap_attention_kernel_vs_float64.
+    The two sides differ in their exponential (expf against __expf), so they are not compared bit for bit.  The tolerance is DERIVED, not
+    measured: each side is already held to a bound against float64 -- the swap side to assert_close(rtol 1e-4, atol 1e-5)
+    (test_swap_attention_kernel_vs_float64), the window side to Report.check's max-error bound with C_OUT (test_win_attn_fwd) -- and
+    two results within those bounds of the truth differ by at most their sum."""
+    import numpy as np
+    from gencomm_amd import _lib
+    heads, B, H, W = 2, 2, 16, 24
+    rng = np.random.RandomState(100 * ws + dh)
+    qkv = rng.standard_normal((B, 3 * heads * dh, H, W)).astype(np.float32)
+    qkv[:, :heads * dh] *= 1.5
+    qkv = torch.from_numpy(qkv)
+    pos = torch.from_numpy(rng.uniform(-1.0, 1.0, (2 * ws - 1, 2 * ws - 1)).astype(np.float32))
+    off_centre = torch.ones_like(pos, dtype=torch.bool)
+    off_centre[ws - 1, ws - 1] = False
+    assert bool((pos != pos.flip(0, 1))[off_centre].all())   # pos[dy][dx] != pos[-dy][-dx]: a table that is not flipped shows
+    table = pos.flatten().flip(0)[:, None].repeat(1, heads).contiguous()
+    q_d, nv = qkv.to(_dev()), torch.ones(B, dtype=torch.int32, device=_dev())
+    swap, win = Guarded((B, heads * dh, H, W)), Guarded((B, heads * dh, H, W))
+    with _lib.kernel_log() as kl:
+        _call("gencomm_swap_attn_fwd", _p(q_d), _p(table.to(_dev())), _p(nv), _p(swap.t), B, 1, heads, dh, ws, H, W, 0, _st())
+        _call("gencomm_win_attn_fwd", _p(q_d), _p(pos.to(_dev())), _p(win.t), B, heads, dh, ws, H, W, _st())
+    assert swap.intact() and win.intact()
+    assert kl.counts == {f"swap_attn_kernel<{dh},{ws}>": 1, _win_kernel_name(ws, dh): 1}, kl.counts
+    truth, f32 = R.win_attn(qkv.double(), pos.double(), heads, dh, ws), R.win_attn(qkv, pos, heads, dh, ws)
+    tol = _bound(truth, f32, C_OUT) + 1e-5 + 1e-4 * truth.abs()
+    err = (swap.t.cpu().double() - win.t.cpu().double()).abs()
+    print(f"swap vs window attention ws {ws} dh {dh}: max difference {float(err.max()):.2e}, smallest tolerance {float(tol.min()):.2e}")
+    assert bool(torch.isfinite(err).all()) and bool((err <= tol).all()), (float(err.max()), float(tol.min()))
 
 
 # ---- agent attention --------------------------------------------------------------------------------------------------------------
