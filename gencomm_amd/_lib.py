@@ -136,6 +136,7 @@ _SIGNATURES = {
     "gencomm_umgm_bwd": (_i, [_p, _p, _p, _p, C.c_ulonglong, _i, _p, _p, _p, _p, _p, _i, _ll, _i, _i, _i, C.POINTER(_i), _i, _p, _ll, _p]),
     "gencomm_rows_wgrad_fixed_scratch_floats": (_ll, [_ll, _i, _i]),
     "gencomm_rows_wgrad_fixed": (_i, [_p, _p, _p, _ll, _i, _i, _p, _ll, _p]),
+    "gencomm_convnext_block_fwd": (_i, [_p] * 11 + [_i] * 4 + [_p]),
     "gencomm_iou3d_pairwise_fwd": (_i, [_p, _i, _p, _i, _i, _p, _p]),
     "gencomm_iou3d_max_boxes": (_i, []),
     "gencomm_iou3d_nms_workspace_bytes": (_ll, [_i]),

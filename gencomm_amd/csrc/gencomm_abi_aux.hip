@@ -1,6 +1,7 @@
 // Second translation unit of libgencomm_hip.so: iou3d_nms (reference extension semantics), the point-cloud voxeliser,
 // the V2X-ViT attention kernels, the sparse 3-D convolutions of the SECOND encoder, the Lift-Splat-Shoot camera encoder
-// the training-time anchor target assignment, the batched lidar front end, CoBEVT's swap attention and V2VNet's message passing.
+// the training-time anchor target assignment, the batched lidar front end, CoBEVT's swap attention, V2VNet's message passing,
+// the CodeFilling codec and STAMP's ConvNeXt block.
 // Kept apart from gencomm_abi.hip so that the rocPRIM templates do not lengthen the hot path's compile.
 #include "../../include/gencomm_hip.h"
 
@@ -9,6 +10,7 @@
 #include "common.h"
 #include "codebook_bwd_kernels.h"
 #include "codebook_kernels.h"
+#include "convnext_kernels.h"
 #include "iou3d_kernels.h"
 #include "loss_kernels.h"
 #include "lss_kernels.h"
@@ -1061,6 +1063,14 @@ int gencomm_rows_wgrad_fixed(const float* g, const float* a, float* dw, long lon
   RowsWgradArgs w{};
   w.G[0] = g; w.A[0] = a; w.out[0] = dw; w.part = scratch; w.rows = rows; w.Co = Co; w.Ci = Ci; w.count = 1;
   return rows_wgrad_launch(w, (hipStream_t)stream);
+}
+
+// ---- STAMP's ConvNeXt block (convnext_kernels.h)
+int gencomm_convnext_block_fwd(const float* x, const float* dw_weight, const float* dw_bias, const float* ln_weight, const float* ln_bias,
+                               const float* w1, const float* b1, const float* w2, const float* b2, const float* gamma, float* y,
+                               int n, int C, int H, int W, void* stream) {
+  CnxArgs a{x, dw_weight, dw_bias, ln_weight, ln_bias, w1, b1, w2, b2, gamma, y, H, W, 0};
+  return convnext_block_launch(a, n, C, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -722,6 +722,18 @@ int gencomm_umgm_bwd(const float* params, const float* x, const unsigned char* k
 long long gencomm_rows_wgrad_fixed_scratch_floats(long long rows, int Co, int Ci);
 int gencomm_rows_wgrad_fixed(const float* g, const float* a, float* dw, long long rows, int Co, int Ci, float* scratch, long long scratch_floats,
                              void* stream);
+/* STAMP's ConvNeXtBlock (opencood/models/stamp_modules/feature_alignnet_modules.py:303-348; the blocks of AdapterConvNext,
+ * stamp_modules/adapter.py:120-144) for all n maps of a call in ONE launch (csrc/convnext_kernels.h; additive, ABI v12):
+ *   y = x + gamma * pwconv2(GELU(pwconv1(LayerNorm_C(dwconv7x7(x)))))
+ * x, y NCHW fp32 [n][C][H][W]; dwconv depthwise 7x7, zero padding 3, with bias (:323); LayerNorm over the channel axis of each pixel, biased
+ * variance, eps 1e-6, weight and bias (:324, channels_last); erf-GELU (:326); pwconv1 C -> 4 C, pwconv2 4 C -> C (:325, :327) on the exact
+ * fp32 MFMA, the [pixels, 4 C] hidden tensor never in memory; gamma [C] (:328), NULL where the reference has `gamma is None`.
+ * Weights as the reference stores them: dw_weight [C][1][7][7], w1 [4 C][C], w2 [C][4 C] (16-byte aligned): there is no prepared form.
+ * C must be 64 or 128, the two instantiations (any other: returns -1, gencomm_last_error() names C); y must not overlap x (neighbouring
+ * tiles read the halo: status 1, nothing launched).  No float atomics: two runs give the same bits. */
+int gencomm_convnext_block_fwd(const float* x, const float* dw_weight, const float* dw_bias, const float* ln_weight, const float* ln_bias,
+                               const float* w1, const float* b1, const float* w2, const float* b2, const float* gamma, float* y,
+                               int n, int C, int H, int W, void* stream);
 /* radix-3 split attention over the three window branches (sub_modules/split_attn.py:31-62): out = sum_r softmax_r(fc2(ReLU(LN(fc1(
  * mean_HW(a + b + c))))))[r] * branch_r (+ residual); fc1 [C][C], fc2 [3 C][C] without biases; scratch >= 4 n C floats; C <= 256 */
 int gencomm_split3_attn_fwd(const float* a, const float* b, const float* c, const float* fc1_w, const float* ln_w, const float* ln_b,
