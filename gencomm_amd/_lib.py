@@ -137,6 +137,8 @@ _SIGNATURES = {
     "gencomm_rows_wgrad_fixed_scratch_floats": (_ll, [_ll, _i, _i]),
     "gencomm_rows_wgrad_fixed": (_i, [_p, _p, _p, _ll, _i, _i, _p, _ll, _p]),
     "gencomm_convnext_block_fwd": (_i, [_p] * 11 + [_i] * 4 + [_p]),
+    "gencomm_convnext_block_bwd_workspace_bytes": (_ll, [_i] * 6),
+    "gencomm_convnext_block_bwd": (_i, [_p] * 21 + [_i] * 6 + [_p, _ll, _p]),
     "gencomm_iou3d_pairwise_fwd": (_i, [_p, _i, _p, _i, _i, _p, _p]),
     "gencomm_iou3d_max_boxes": (_i, []),
     "gencomm_iou3d_nms_workspace_bytes": (_ll, [_i]),

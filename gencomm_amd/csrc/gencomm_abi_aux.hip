@@ -11,6 +11,7 @@
 #include "codebook_bwd_kernels.h"
 #include "codebook_kernels.h"
 #include "convnext_kernels.h"
+#include "convnext_bwd_kernels.h"
 #include "iou3d_kernels.h"
 #include "loss_kernels.h"
 #include "lss_kernels.h"
@@ -1071,6 +1072,62 @@ int gencomm_convnext_block_fwd(const float* x, const float* dw_weight, const flo
                                int n, int C, int H, int W, void* stream) {
   CnxArgs a{x, dw_weight, dw_bias, ln_weight, ln_bias, w1, b1, w2, b2, gamma, y, H, W, 0};
   return convnext_block_launch(a, n, C, (hipStream_t)stream);
+}
+
+// ---- its adjoint (convnext_bwd_kernels.h)
+static int cnx_bwd_check_shape(int n, int C, int H, int W, int dx_only, int slabs) {
+  if (C != 64 && C != 128) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "convnext block backward: C must be 64 or 128 (got %d)", C);
+    return fail(GC_ERR_ARG, msg);
+  }
+  GC_CHECK_ARG(n >= 1 && n <= 65535 && H >= 1 && W >= 1, "convnext block backward: 1..65535 maps (n), positive H / W");
+  GC_CHECK_ARG((H + kCnxTileH - 1) / kCnxTileH <= 65535, "convnext block backward: H must be at most 262140");
+  GC_CHECK_ARG((long long)n * ((H + kCnxTileH - 1) / kCnxTileH) * ((W + kCnxTileW - 1) / kCnxTileW) <= 0x7fffffffll,
+               "convnext block backward: n, H, W give more than 2^31 - 1 tiles");
+  GC_CHECK_ARG(dx_only == 0 || dx_only == 1, "convnext block backward: dx_only must be 0 or 1");
+  GC_CHECK_ARG(slabs >= 0 && slabs <= 65535, "convnext block backward: slabs must be 0 (automatic) .. 65535");
+  return GC_OK;
+}
+
+long long gencomm_convnext_block_bwd_workspace_bytes(int n, int C, int H, int W, int dx_only, int slabs) {
+  if (cnx_bwd_check_shape(n, C, H, W, dx_only, slabs) != GC_OK) return -1;
+  return cnx_bwd_plan(n, C, H, W, dx_only, slabs).total * (long long)sizeof(float);
+}
+
+int gencomm_convnext_block_bwd(const float* x, const float* dy, const float* dw_weight, const float* dw_bias, const float* ln_weight,
+                               const float* ln_bias, const float* w1, const float* b1, const float* w2, const float* b2, const float* gamma,
+                               float* dx, float* d_dw_weight, float* d_dw_bias, float* d_ln_weight, float* d_ln_bias, float* d_w1, float* d_b1,
+                               float* d_w2, float* d_b2, float* d_gamma, int dx_only, int slabs, int n, int C, int H, int W, void* workspace,
+                               long long workspace_bytes, void* stream) {
+  if (int rc = cnx_bwd_check_shape(n, C, H, W, dx_only, slabs)) return rc;
+  GC_CHECK_ARG(x && dy && dx, "convnext block backward: null pointer (x, dy, dx)");
+  GC_CHECK_ARG(dw_weight && dw_bias && ln_weight && ln_bias && w1 && b1 && w2 && b2, "convnext block backward: null pointer (a parameter other than gamma)");
+  GC_CHECK_ARG(dx_only || (d_dw_weight && d_dw_bias && d_ln_weight && d_ln_bias && d_w1 && d_b1 && d_w2 && d_b2),
+               "convnext block backward: null pointer (a parameter gradient without dx_only)");
+  GC_CHECK_ARG(dx_only || gamma == nullptr || d_gamma, "convnext block backward: null pointer (d_gamma with gamma and without dx_only)");
+  GC_CHECK_ARG((((uintptr_t)w1 | (uintptr_t)workspace) & 15) == 0, "convnext block backward: w1 and workspace must be 16-byte aligned");
+  GC_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 3) == 0, "convnext block backward: x, dy and dx must be 4-byte aligned");
+  const size_t bytes = (size_t)n * C * H * W * sizeof(float);
+  const uintptr_t xb = (uintptr_t)x, db = (uintptr_t)dx, yb = (uintptr_t)dy;
+  GC_CHECK_ARG(xb + bytes <= db || db + bytes <= xb, "convnext block backward: dx must not alias x (the tap gradients read x's halo)");
+  GC_CHECK_ARG(db == yb || yb + bytes <= db || db + bytes <= yb, "convnext block backward: dx must be dy itself or not overlap dy");
+  const CnxBwdPlan p = cnx_bwd_plan(n, C, H, W, dx_only, slabs);
+  if (workspace == nullptr || workspace_bytes < p.total * (long long)sizeof(float))
+    return fail(GC_ERR_WORKSPACE, "convnext block backward: workspace too small (gencomm_convnext_block_bwd_workspace_bytes)");
+  float* ws = (float*)workspace;
+  CnxBwdArgs a{};
+  a.x = x; a.dy = dy; a.dw_w = dw_weight; a.dw_b = dw_bias; a.ln_w = ln_weight; a.ln_b = ln_bias; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2;
+  a.gamma = gamma; a.dx = dx;
+  a.g_dw_w = d_dw_weight; a.g_dw_b = d_dw_bias; a.g_ln_w = d_ln_weight; a.g_ln_b = d_ln_bias; a.g_w1 = d_w1; a.g_b1 = d_b1; a.g_w2 = d_w2;
+  a.g_b2 = d_b2; a.g_gamma = gamma != nullptr ? d_gamma : nullptr;
+  a.w1t = ws + p.w1t; a.w2g = ws + p.w2g; a.xh = ws + p.xh; a.dd = ws + p.dd; a.p_ln = ws + p.p_ln;
+  if (!dx_only) {
+    a.p_w = ws + p.p_w; a.p_dw = ws + p.p_dw; a.s_red = ws + p.s_red; a.sdy = ws + p.sdy;
+  }
+  a.n = n; a.H = H; a.W = W; a.tx = p.tx; a.ty = p.ty; a.tiles = p.tiles; a.slabs = p.slabs; a.tps = p.tps; a.dx_only = dx_only;
+  a.vec = (W % 4 == 0 && ((yb | db) & 15) == 0) ? 1 : 0;
+  return convnext_block_bwd_launch(a, C, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -2,7 +2,14 @@
 
 In STAMP every non-protocol agent pushes its BEV map through an ``Adapter`` into the protocol feature space and every receiver pulls it
 back through a ``Reverter``; both are built from the same constructor dict, ``{"core_method": ..., "args": {...}}``. This module is the
-component, for inference; the baseline's shell and its ``adapter_loss`` criterion are not here.
+component; the baseline's shell and its ``adapter_loss`` criterion are not here.
+
+Training is opt-in: ``Adapter(args, trainable=True)`` / ``Reverter(args, trainable=True)`` send a grad-enabled call that has something
+to differentiate through ONE ``torch.autograd.Function`` per call (``convnext_bwd.py``): the same forward launches and bits, a tape of
+the module input and ``num_of_blocks + 1`` maps of ``[n, dim, H, W]``, and per block the six launches of ``gencomm_convnext_block_bwd``
+(csrc/convnext_bwd_kernels.h), which recompute the hidden tensor tile by tile instead of keeping it. The default constructors refuse a
+grad-enabled call as before; under ``torch.no_grad()``, or with nothing to differentiate, both run the inference path. ``smoothing``
+gets no gradient (the reference's forward never uses it). The ``state_dict`` is the same either way.
 
 ``core_method``:
 
@@ -214,12 +221,14 @@ def _build_core(args, what):
 
 class _Wrapper(nn.Module):
     _child = None
+    trainable = False   # True: a grad-enabled call goes through convnext_bwd.run_trainable (one autograd Function per call)
 
     def _core(self):
         return getattr(self, self._child)
 
     def forward(self, x):
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if grad and not self.trainable:
             raise NotImplementedError("stamp adapter training is not implemented (the backward of the fused ConvNeXt block is missing): call under "
                                       "torch.no_grad(), or freeze the parameters and detach the input")
         require_gpu(x, f"stamp {self._child}")
@@ -228,7 +237,10 @@ class _Wrapper(nn.Module):
         core = self._core()
         if x.shape[1] != core.in_channels:
             raise ValueError(f"stamp {self._child}: input has {x.shape[1]} channels, the module was built with in_channels {core.in_channels}")
-        with torch.no_grad():
+        if grad and (x.requires_grad or any(p.requires_grad for n, p in core.named_parameters() if not n.startswith("smoothing."))):
+            from .convnext_bwd import run_trainable
+            return run_trainable(core, x)
+        with torch.no_grad():   # nothing to differentiate (smoothing is not part of the forward): the inference path
             return core.run(x)
 
 
@@ -236,8 +248,9 @@ class Adapter(_Wrapper):
     """``Adapter(args)(x)``: x [agents, in_channels, H, W] -> [agents, out_channels, H, W] in the protocol space."""
     _child = "adapter"
 
-    def __init__(self, args):
+    def __init__(self, args, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.adapter = _build_core(args, "adapter")
 
 
@@ -245,6 +258,7 @@ class Reverter(_Wrapper):
     """``Reverter(args)(x)``: the protocol-space map back into the receiver's feature space."""
     _child = "reverter"
 
-    def __init__(self, args):
+    def __init__(self, args, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.reverter = _build_core(args, "reverter")

@@ -734,6 +734,20 @@ int gencomm_rows_wgrad_fixed(const float* g, const float* a, float* dw, long lon
 int gencomm_convnext_block_fwd(const float* x, const float* dw_weight, const float* dw_bias, const float* ln_weight, const float* ln_bias,
                                const float* w1, const float* b1, const float* w2, const float* b2, const float* gamma, float* y,
                                int n, int C, int H, int W, void* stream);
+/* The adjoint of that block (csrc/convnext_bwd_kernels.h; additive, ABI v12).  Given the block's input x, dy and the parameters it writes
+ * dx and, unless dx_only, the gradient of every parameter (d_gamma ignored where gamma is NULL); every output element is WRITTEN once, no
+ * float atomics, parameter gradients are fixed-order sums of per-slab partials: two runs give the same bits.  u and h are recomputed per
+ * 64-pixel tile and 64-column hidden chunk; nothing of size [pixels, 4 C] is stored: the workspace holds two [n][C][H][W] maps, per-tile
+ * and per-slab partial sums and two re-laid weight matrices (gencomm_convnext_block_bwd_workspace_bytes; 16-byte aligned).  One call is at
+ * most 6 launches (3 with dx_only = 1, which serves a frozen block with a trainable input).  slabs: how many pixel slabs the parameter
+ * gradients are summed over, 0 = automatic (at most 192).  Status 1 and nothing launched for: C other than 64 / 128, a null pointer, a
+ * workspace that is too small (status 2), dx overlapping x, dx overlapping dy without being dy itself (dx == dy is allowed). */
+long long gencomm_convnext_block_bwd_workspace_bytes(int n, int C, int H, int W, int dx_only, int slabs);
+int gencomm_convnext_block_bwd(const float* x, const float* dy, const float* dw_weight, const float* dw_bias, const float* ln_weight,
+                               const float* ln_bias, const float* w1, const float* b1, const float* w2, const float* b2, const float* gamma,
+                               float* dx, float* d_dw_weight, float* d_dw_bias, float* d_ln_weight, float* d_ln_bias, float* d_w1, float* d_b1,
+                               float* d_w2, float* d_b2, float* d_gamma, int dx_only, int slabs, int n, int C, int H, int W, void* workspace,
+                               long long workspace_bytes, void* stream);
 /* radix-3 split attention over the three window branches (sub_modules/split_attn.py:31-62): out = sum_r softmax_r(fc2(ReLU(LN(fc1(
  * mean_HW(a + b + c))))))[r] * branch_r (+ residual); fc1 [C][C], fc2 [3 C][C] without biases; scratch >= 4 n C floats; C <= 256 */
 int gencomm_split3_attn_fwd(const float* a, const float* b, const float* c, const float* fc1_w, const float* ln_w, const float* ln_b,
