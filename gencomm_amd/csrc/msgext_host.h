@@ -65,21 +65,25 @@ inline int msgext_enqueue(const MsgExtPlan& p, const float* raw, const float* x,
     int tw, th;
     tile_dims(tc, &tw, &th);
     const dim3 grid(cdiv(W, tw), cdiv(H, th), n);
+    GC_KLOG(tc == TILE_64x16 ? "conv3x3_cN_kernel<64,16,4,5>" : tc == TILE_32x16 ? "conv3x3_cN_kernel<32,16,4,5>" : "conv3x3_cN_kernel<32,8,1,5>");
     if (tc == TILE_64x16) conv3x3_cN_kernel<64, 16, 4, 5><<<grid, 256, 0, st>>>(a);
     else if (tc == TILE_32x16) conv3x3_cN_kernel<32, 16, 4, 5><<<grid, 128, 0, st>>>(a);
     else conv3x3_cN_kernel<32, 8, 1, 5><<<grid, 256, 0, st>>>(a);
   }
   {
     DcnArgs a{x, F(w.off), F(w.wDcn), raw + p.db, F(w.b1), F(w.colsum), C, H, W};
+    GC_KLOG((long long)cdiv(HW, 256) * n < 512 ? "dcn_csplit_kernel" : "dcn_kernel");
     if ((long long)cdiv(HW, 256) * n < 512) dcn_csplit_kernel<<<dim3(cdiv(HW, 64), n), 256, 0, st>>>(a);   // small maps: 4x the workgroups, a quarter of the chain per wave
     else dcn_kernel<<<dim3(cdiv(HW, 256), n), 256, 0, st>>>(a);
   }
   {
     MsgGateArgs a{F(w.colsum), raw + p.a1w, raw + p.a1b, raw + p.a3w, raw + p.a3b, F(w.gate), 1.0f / (float)HW};
+    GC_KLOG("msg_gate_kernel");
     msg_gate_kernel<<<n, 64, 0, st>>>(a);
   }
   {
     MsgFuseArgs a{F(w.b1), F(w.gate), F(w.wFuse), raw + p.f0b, raw + p.f2w, raw + p.f2b, out, HW};
+    GC_KLOG("msg_fuse_kernel");
     msg_fuse_kernel<<<dim3(cdiv(HW, 256), n), 256, 0, st>>>(a);
   }
   GC_HIP(hipGetLastError());
