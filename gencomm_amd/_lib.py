@@ -139,6 +139,10 @@ _SIGNATURES = {
     "gencomm_convnext_block_fwd": (_i, [_p] * 11 + [_i] * 4 + [_p]),
     "gencomm_convnext_block_bwd_workspace_bytes": (_ll, [_i] * 6),
     "gencomm_convnext_block_bwd": (_i, [_p] * 21 + [_i] * 6 + [_p, _ll, _p]),
+    "gencomm_gconv3x3_prepare": (_i, [_p, _p, _i, _p]),
+    "gencomm_gconv3x3_fwd": (_i, [_p] * 5 + [_i] * 7 + [_p]),
+    "gencomm_pyramid_score_fwd": (_i, [_p] * 6 + [_i] * 4 + [_p]),
+    "gencomm_warp_weightfuse_fwd": (_i, [_p] * 5 + [_i] * 5 + [_p]),
     "gencomm_iou3d_pairwise_fwd": (_i, [_p, _i, _p, _i, _i, _p, _p]),
     "gencomm_iou3d_max_boxes": (_i, []),
     "gencomm_iou3d_nms_workspace_bytes": (_ll, [_i]),

@@ -354,6 +354,66 @@ def conv2d_hip(x: torch.Tensor, conv: nn.Module, bn: Optional[nn.BatchNorm2d] = 
     return out
 
 
+GCONV_GROUPS = 32
+GCONV_WIDTHS = (4, 8, 16)
+
+
+def gconv3x3_check(conv: nn.Module) -> int:
+    """Channels per group of a grouped 3x3 layer the HIP kernel covers (Conv2d(C, C, 3, padding=1, groups=32), 4 / 8 / 16 channels
+    per group, stride 1 | 2); anything else raises naming it. No device is needed for the check."""
+    if not isinstance(conv, nn.Conv2d) or conv.kernel_size != (3, 3) or conv.padding != (1, 1) or conv.dilation != (1, 1) \
+            or conv.stride not in ((1, 1), (2, 2)) or conv.padding_mode != "zeros":
+        raise NotImplementedError(f"grouped convolution: only Conv2d 3x3, padding 1, dilation 1, stride 1 | 2 is built (got {conv})")
+    cpg = conv.in_channels // conv.groups
+    if conv.groups != GCONV_GROUPS or cpg not in GCONV_WIDTHS or conv.in_channels != conv.groups * cpg:
+        raise NotImplementedError(f"grouped convolution: unsupported group width ({conv.groups} groups x {conv.in_channels / conv.groups:g} "
+                                  f"channels; built: {GCONV_GROUPS} groups x {GCONV_WIDTHS} channels)")
+    if conv.out_channels != conv.in_channels:
+        raise NotImplementedError(f"grouped convolution: C_in != C_out ({conv.in_channels} -> {conv.out_channels}) is not built")
+    return cpg
+
+
+def gconv3x3_hip(x: torch.Tensor, conv: nn.Conv2d, bn: Optional[nn.BatchNorm2d] = None, relu: bool = False) -> torch.Tensor:
+    """act(BN_eval(conv(x))) for the grouped 3x3 of the ResNeXt ``Bottleneck`` as one launch of ``gencomm_gconv3x3_fwd``: the same
+    per-module cache of the prepared weight and the folded BatchNorm as ``conv2d_hip``. Inference only: batch statistics and
+    gradients through this layer are not built and raise."""
+    cpg = gconv3x3_check(conv)
+    params = [p for p in (conv.weight, conv.bias) + ((bn.weight, bn.bias) if bn is not None else ()) if p is not None]
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+        raise NotImplementedError("grouped convolution: the backward is not built (pyramid training is a later change)")
+    if bn is not None and bn_batch_statistics(bn):
+        raise NotImplementedError("grouped convolution: BatchNorm batch statistics (train() mode) are not built")
+    require_gpu(x, "gconv3x3_hip")
+    x = f32c(x)
+    n, c, H, W = x.shape
+    if c != conv.in_channels:
+        raise ValueError(f"expected {conv.in_channels} input channels, got {c}")
+    l, st, w = _lib.lib(), stream_ptr(x.device), conv.weight
+    bnp = (bn.weight, bn.bias, bn.running_mean, bn.running_var) if bn is not None else (None,) * 4
+    key = _versions(w, conv.bias, *bnp, getattr(bn, "num_batches_tracked", None)) + (str(x.device),)
+    cache = getattr(conv, "_gc_cache", None)
+    if cache is None or cache[0] != key:
+        packed = torch.empty(w.numel(), dtype=torch.float32, device=x.device)
+        _lib.check(l.gencomm_gconv3x3_prepare(ptr(f32c(w.detach())), ptr(packed), cpg, st), "gencomm_gconv3x3_prepare")
+        b = f32c(conv.bias.detach()) if conv.bias is not None else None
+        if bn is None:
+            from .train_ops import _unit_scale_shift
+            unit = _unit_scale_shift(c, x.device)
+            ss = (unit[0], b if b is not None else unit[1])
+        else:
+            ss = torch.empty(2, c, dtype=torch.float32, device=x.device)
+            d = [f32c(t.detach()) if t is not None else None for t in bnp]
+            _lib.check(l.gencomm_conv2d_fold(ptr(d[0]), ptr(d[1]), ptr(d[2]), ptr(d[3]), ptr(b), float(bn.eps), c, ptr(ss[0]), ptr(ss[1]), st),
+                       "gencomm_conv2d_fold")
+        cache = (key, packed, ss)
+        conv._gc_cache = cache
+    _, packed, ss = cache
+    s = conv.stride[0]
+    out = torch.empty(n, c, (H - 1) // s + 1, (W - 1) // s + 1, dtype=torch.float32, device=x.device)
+    _lib.check(l.gencomm_gconv3x3_fwd(ptr(x), ptr(packed), ptr(ss[0]), ptr(ss[1]), ptr(out), n, c, cpg, H, W, s, int(relu), st), "gencomm_gconv3x3_fwd")
+    return out
+
+
 class BaseBEVBackbone(nn.Module):
     """Constructor mirrors base_bev_backbone.py:7-92 (same Sequential indices => same checkpoint keys)."""
 

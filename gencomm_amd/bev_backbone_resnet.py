@@ -10,7 +10,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .bev_backbone import conv2d_hip
+from .bev_backbone import conv2d_hip, gconv3x3_hip
 
 
 def conv3x3(in_planes, out_planes, stride=1):
@@ -40,10 +40,37 @@ class BasicBlock(nn.Module):  # resblock.py:18-64
         return conv2d_hip(out, self.conv2, self.bn2, relu=True, residual=identity)      # relu(bn2(conv2(out)) + identity)
 
 
-class ResNetModified(nn.Module):  # resblock.py:125-219 (BasicBlock only: what ResNetBEVBackbone instantiates)
-    def __init__(self, block, layers, layer_strides, num_filters, inplanes=64):
+class Bottleneck(nn.Module):  # resblock.py:67-122, with the expansion 1 that PyramidFusion sets on the reference's class (pyramid_fuse.py:72)
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64):
+        super().__init__()
+        width = int(planes * (base_width / 64.)) * groups
+        self.conv1 = conv1x1(inplanes, width)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = nn.Conv2d(width, width, kernel_size=3, stride=stride, padding=1, groups=groups, bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3 = conv1x1(width, planes * self.expansion)
+        self.bn3 = nn.BatchNorm2d(planes * self.expansion)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x):
+        identity = x if self.downsample is None else conv2d_hip(x, self.downsample[0], self.downsample[1], relu=False)
+        out = conv2d_hip(x, self.conv1, self.bn1, relu=True)
+        if self.conv2.groups == 1:
+            out = conv2d_hip(out, self.conv2, self.bn2, relu=True)
+        else:
+            out = gconv3x3_hip(out, self.conv2, self.bn2, relu=True)                    # the grouped 3x3: gencomm_gconv3x3_fwd
+        return conv2d_hip(out, self.conv3, self.bn3, relu=True, residual=identity)      # relu(bn3(conv3(out)) + identity)
+
+
+class ResNetModified(nn.Module):  # resblock.py:125-219 (BasicBlock: ResNetBEVBackbone; Bottleneck with groups: PyramidFusion's resnext)
+    def __init__(self, block, layers, layer_strides, num_filters, inplanes=64, groups=1, width_per_group=64):
         super().__init__()
         self.inplanes = inplanes
+        self.groups, self.base_width = groups, width_per_group
         self.layernum = len(num_filters)
         for i in range(self.layernum):
             setattr(self, f"layer{i}", self._make_layer(block, num_filters[i], layers[i], stride=layer_strides[i]))
@@ -58,10 +85,11 @@ class ResNetModified(nn.Module):  # resblock.py:125-219 (BasicBlock only: what R
         downsample = None
         if stride != 1 or self.inplanes != planes * block.expansion:
             downsample = nn.Sequential(conv1x1(self.inplanes, planes * block.expansion, stride), nn.BatchNorm2d(planes * block.expansion))
-        layers = [block(self.inplanes, planes, stride, downsample)]
+        extra = (self.groups, self.base_width) if block is Bottleneck else ()
+        layers = [block(self.inplanes, planes, stride, downsample, *extra)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            layers.append(block(self.inplanes, planes))
+            layers.append(block(self.inplanes, planes, 1, None, *extra))
         return nn.Sequential(*layers)
 
     def forward(self, x):

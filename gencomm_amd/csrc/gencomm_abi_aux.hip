@@ -21,6 +21,9 @@
 #include "target_kernels.h"
 #include "v2v_kernels.h"
 #include "v2xvit_kernels.h"
+#include "pyramid_kernels.h"   // out of alphabetical order on purpose: fuse_cell.h must first be parsed where v2v_kernels.h includes it (the
+                               // headers between iou3d_kernels.h and swap_attn_bwd_kernels.h run under `fp contract(off)`), or the warp kernels of
+                               // this unit stop matching the fusion kernels of gencomm_abi.hip bit for bit
 #include "voxel_batch_kernels.h"
 #include "voxel_kernels.h"
 
@@ -1128,6 +1131,58 @@ int gencomm_convnext_block_bwd(const float* x, const float* dy, const float* dw_
   a.n = n; a.H = H; a.W = W; a.tx = p.tx; a.ty = p.ty; a.tiles = p.tiles; a.slabs = p.slabs; a.tps = p.tps; a.dx_only = dx_only;
   a.vec = (W % 4 == 0 && ((yb | db) & 15) == 0) ? 1 : 0;
   return convnext_block_bwd_launch(a, C, (hipStream_t)stream);
+}
+
+// ---- HEAL's PyramidFusion (pyramid_kernels.h)
+static int gconv_check(int n, int C, int cpg, int H, int W, int stride) {
+  if (cpg != 4 && cpg != 8 && cpg != 16) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "grouped 3x3: unsupported group width %d channels per group (built: 4, 8, 16 with 32 groups)", cpg);
+    return fail(GC_ERR_ARG, msg);
+  }
+  if (C != 32 * cpg) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "grouped 3x3: C must be 32 groups x %d = %d channels in AND out (got %d)", cpg, 32 * cpg, C);
+    return fail(GC_ERR_ARG, msg);
+  }
+  GC_CHECK_ARG(stride == 1 || stride == 2, "grouped 3x3: stride must be 1 or 2 (dilation 1, padding 1)");
+  GC_CHECK_ARG(n >= 1 && n <= 65535 && H >= 1 && W >= 1, "grouped 3x3: 1..65535 maps (n), positive H / W");
+  const long long Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  GC_CHECK_ARG(((Ho + kGcTileH - 1) / kGcTileH) * ((Wo + kGcTileW - 1) / kGcTileW) <= 0x7fffffffll && (long long)H * W <= 0x7fffffffll,
+               "grouped 3x3: the map has more than 2^31 - 1 tiles or pixels");
+  return GC_OK;
+}
+
+int gencomm_gconv3x3_prepare(const float* weight, float* packed, int cpg, void* stream) {
+  if (int rc = gconv_check(1, 32 * cpg, cpg, 1, 1, 1)) return rc;
+  GC_CHECK_ARG(weight && packed, "grouped 3x3 prepare: null pointer");
+  const int total = 32 * cpg * cpg * 9;
+  gconv3x3_pack_kernel<<<(total + 255) / 256, 256, 0, (hipStream_t)stream>>>(weight, packed, cpg);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_gconv3x3_fwd(const float* x, const float* packed, const float* scale, const float* shift, float* y, int n, int C, int cpg, int H, int W,
+                         int stride, int relu, void* stream) {
+  if (int rc = gconv_check(n, C, cpg, H, W, stride)) return rc;
+  GC_CHECK_ARG(x && packed && scale && shift && y, "grouped 3x3: null pointer");
+  return gconv3x3_enqueue(x, packed, scale, shift, y, n, cpg, H, W, stride, relu ? 1 : 0, (hipStream_t)stream);
+}
+
+int gencomm_pyramid_score_fwd(const float* x, const float* weight, const float* bias, const int* rect, float* occ, float* score, int n, int C, int H,
+                              int W, void* stream) {
+  GC_CHECK_ARG(x && weight && bias && occ && score, "pyramid score: null pointer (rect alone may be null)");
+  GC_CHECK_ARG(n >= 1 && n <= 65535 && C >= 1 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffll - 64, "pyramid score: bad n/C/H/W");
+  PyrScoreArgs a{x, weight, bias, rect, occ, score, C, H, W};
+  return pyramid_score_enqueue(a, n, (hipStream_t)stream);
+}
+
+int gencomm_warp_weightfuse_fwd(const float* x, const float* score, const double* theta, const int* scene_off, float* out, int B, int n, int C, int H,
+                                int W, void* stream) {
+  GC_CHECK_ARG(x && score && theta && scene_off && out, "weighted fuse: null pointer");
+  GC_CHECK_ARG(B >= 1 && B <= 65535 && n >= B && C >= 1 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffll - 64, "weighted fuse: bad B/n/C/H/W");
+  WeightFuseArgs a{x, score, theta, scene_off, out, C, H, W, 0};
+  return warp_weightfuse_enqueue(a, B, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -734,6 +734,29 @@ int gencomm_rows_wgrad_fixed(const float* g, const float* a, float* dw, long lon
 int gencomm_convnext_block_fwd(const float* x, const float* dw_weight, const float* dw_bias, const float* ln_weight, const float* ln_bias,
                                const float* w1, const float* b1, const float* w2, const float* b2, const float* gamma, float* y,
                                int n, int C, int H, int W, void* stream);
+/* HEAL's PyramidFusion (opencood/models/fuse_modules/pyramid_fuse.py; csrc/pyramid_kernels.h; additive, ABI v12).  fp32 NCHW throughout, no
+ * float atomics: two runs give the same bits.
+ *   gencomm_gconv3x3_prepare   weight [C][cpg][3][3] of a Conv2d(C, C, 3, padding 1, groups 32) -> packed [32][cpg][9][cpg] (32 cpg cpg 9
+ *                              floats): packed[((g cpg + ci) 9 + tap) cpg + co] = weight[g cpg + co][ci][tap]
+ *   gencomm_gconv3x3_fwd       y = act(scale * conv3x3_grouped(x) + shift), conv2 of the ResNeXt Bottleneck (sub_modules/resblock.py:67-122 with
+ *                              groups 32, width_per_group 4).  x [n][C][H][W], y [n][C][Ho][Wo], Ho = (H - 1) / stride + 1; cpg in {4, 8, 16},
+ *                              C = 32 cpg in and out, stride 1 | 2, padding 1, dilation 1: anything else returns -1 and
+ *                              gencomm_last_error() names it.  scale / shift [C]: gencomm_conv2d_fold's output; relu != 0: ReLU.
+ *   gencomm_pyramid_score_fwd  the single-supervision head of one level (pyramid_fuse.py:143-162): occ = Conv2d(C, 1, 1)(x) (weight [C],
+ *                              bias [1]), score = (sigmoid(occ) + 1e-4) * mask; both [n][1][H][W].  rect [n][4] int32 = (h0, h1, w0, w1):
+ *                              mask = 1 inside rows [h0, h1) x columns [w0, w1) and 0 outside (an empty range: 0 everywhere); h0 < 0 = no
+ *                              mask for this agent; rect NULL = no mask at all.
+ *   gencomm_warp_weightfuse_fwd  weighted_fuse (pyramid_fuse.py:17-63), arguments as gencomm_warp_attfuse_fwd plus score [n][1][H][W]: per
+ *                              output pixel the warped score of every agent of the scene (warp_affine_simple, align_corners False), exact 0
+ *                              -> -inf, softmax over the agents, out[c] = sum_j p_j warp(x_j)[c]; a pixel where every agent is -inf is
+ *                              exactly 0 (the reference's NaN -> 0).  At most 8 agents per scene. */
+int gencomm_gconv3x3_prepare(const float* weight, float* packed, int cpg, void* stream);
+int gencomm_gconv3x3_fwd(const float* x, const float* packed, const float* scale, const float* shift, float* y, int n, int C, int cpg, int H, int W,
+                         int stride, int relu, void* stream);
+int gencomm_pyramid_score_fwd(const float* x, const float* weight, const float* bias, const int* rect, float* occ, float* score, int n, int C, int H,
+                              int W, void* stream);
+int gencomm_warp_weightfuse_fwd(const float* x, const float* score, const double* theta, const int* scene_off, float* out, int B, int n, int C, int H,
+                                int W, void* stream);
 /* The adjoint of that block (csrc/convnext_bwd_kernels.h; additive, ABI v12).  Given the block's input x, dy and the parameters it writes
  * dx and, unless dx_only, the gradient of every parameter (d_gamma ignored where gamma is NULL); every output element is WRITTEN once, no
  * float atomics, parameter gradients are fixed-order sums of per-slab partials: two runs give the same bits.  u and h are recomputed per
