@@ -18,6 +18,8 @@ Public surface mirrors the reference's plugin API:
     Adapter(args), Reverter(args)      opencood/models/stamp_modules/adapter.py:759, :783 (STAMP's adapter / reverter; components, inference)
     PyramidFusion(model_cfg)           opencood/models/fuse_modules/pyramid_fuse.py:65 (HEAL's pyramid backbone + fusion; a component, inference)
     weighted_fuse(x, score, ...)       opencood/models/fuse_modules/pyramid_fuse.py:17
+    MPDAAlign(args)                    opencood/models/heter_model_baseline_w_mpda.py:232-262 (MPDA's feature aligner; a component, inference), with
+    LearnableResizer, SwapFusionEncoder, CrossDomainFusionEncoder, DAImgHead   opencood/models/mpda_modules/
 
 All compute runs in hand-written HIP kernels behind the C ABI of ``include/gencomm_hip.h``.
 """
@@ -29,6 +31,7 @@ from .fusion import AttFusion, MaxFusion, normalize_pairwise_tfm, regroup
 from .lift_splat_shoot import LiftSplatShoot
 from .message_extractor import MessageExtractorv2
 from .point_pillar_depth_loss import PointPillarDepthLoss
+from .mpda import CrossDomainFusionEncoder, DAImgHead, LearnableResizer, MPDAAlign, SwapFusionEncoder
 from .pyramid_fuse import PyramidFusion, weighted_fuse
 from .stamp_adapter import Adapter, Reverter
 from .unet import DiffusionUNet
@@ -48,5 +51,5 @@ def set_denoise_dtype(dtype) -> None:
     _lib.check(_lib.lib().gencomm_set_mode(_lib.MODE_ARITH, value), "gencomm_set_mode")
 
 
-__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "MaxFusion", "Who2comFusion", "CoBEVT", "V2VNetFusion", "UMGMQuantizer", "Adapter", "Reverter", "PyramidFusion", "weighted_fuse", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "regroup", "normalize_pairwise_tfm",
+__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "MaxFusion", "Who2comFusion", "CoBEVT", "V2VNetFusion", "UMGMQuantizer", "Adapter", "Reverter", "PyramidFusion", "weighted_fuse", "MPDAAlign", "LearnableResizer", "SwapFusionEncoder", "CrossDomainFusionEncoder", "DAImgHead", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "regroup", "normalize_pairwise_tfm",
            "set_denoise_dtype"]

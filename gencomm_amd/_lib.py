@@ -143,6 +143,8 @@ _SIGNATURES = {
     "gencomm_gconv3x3_fwd": (_i, [_p] * 5 + [_i] * 7 + [_p]),
     "gencomm_pyramid_score_fwd": (_i, [_p] * 6 + [_i] * 4 + [_p]),
     "gencomm_warp_weightfuse_fwd": (_i, [_p] * 5 + [_i] * 5 + [_p]),
+    "gencomm_quad_attn_fwd": (_i, [_p] * 5 + [_i] * 9 + [_p]),
+    "gencomm_resize_bilinear_fwd": (_i, [_p, _p] + [_i] * 6 + [_p]),
     "gencomm_iou3d_pairwise_fwd": (_i, [_p, _i, _p, _i, _i, _p, _p]),
     "gencomm_iou3d_max_boxes": (_i, []),
     "gencomm_iou3d_nms_workspace_bytes": (_ll, [_i]),

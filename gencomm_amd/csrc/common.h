@@ -240,6 +240,7 @@ __device__ __forceinline__ float sigmoid_f(float x) {
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
 }
 __device__ __forceinline__ float silu_f(float x) { return x * sigmoid_f(x); }
+__device__ __forceinline__ float leaky_relu_f(float x) { return x > 0.f ? x : 0.01f * x; }   // nn.LeakyReLU() (negative_slope 0.01)
 __device__ __forceinline__ float gelu_erf_f(float x) {
   // erf-GELU (nn.GELU() default) with erf(t) = 1 - 2^(-t Q(t)), t = |x| / sqrt(2) clamped to 4.3 (erf(4.3) = 1 - 1.2e-9),
   // Q a degree-6 polynomial fitted to -log2(erfc(t)) / t on [0, 4.3] (reweighted least squares on Chebyshev nodes,

@@ -342,7 +342,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_h3_kernel(const Conv2dArgs a) {
       }
       float v = fmaf((acc[g][reg] + accT[g][reg]) * (a.wsc[gco] * inv_xs), a.scale[co], a.shift[co]);
       if (a.relu == 1) v = fmaxf(v, 0.f);
-      else if (a.relu == 2) v = gelu_erf_f(v);
+      else if (a.relu == 2) v = gelu_erf_f(v); else if (a.relu == 4) v = leaky_relu_f(v);
       if (rn != nullptr) v += rn[oi];
       if (a.relu == 3) v = fmaxf(v, 0.f);
       yn[oi] = v;
@@ -631,7 +631,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_h3l_kernel(const Conv2dArgs a, 
       }
       float v = fmaf((acc[g][reg] + accT[g][reg]) * (a.wsc[gco] * inv_xs), a.scale[co], a.shift[co]);
       if (a.relu == 1) v = fmaxf(v, 0.f);
-      else if (a.relu == 2) v = gelu_erf_f(v);
+      else if (a.relu == 2) v = gelu_erf_f(v); else if (a.relu == 4) v = leaky_relu_f(v);
       if (rn != nullptr) v += rn[oi];
       if (a.relu == 3) v = fmaxf(v, 0.f);
       yn[oi] = v;

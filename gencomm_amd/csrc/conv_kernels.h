@@ -34,7 +34,7 @@ struct Conv2dArgs {
   const float* shift;  // [Cout]
   float* y;            // [N][out_ctotal][Ho*ups][Wo*ups], this layer writes channels [out_coff, out_coff + Cout)
   int Cin, H, W, CoutP, Ho, Wo;
-  int stride, pad, relu /* 0 none, 1 ReLU, 2 erf-GELU, 3 ReLU after the residual */, ups, out_ctotal, out_coff;
+  int stride, pad, relu /* 0 none, 1 ReLU, 2 erf-GELU, 3 ReLU after the residual, 4 LeakyReLU(0.01) */, ups, out_ctotal, out_coff;
   const float* res = nullptr;  // optional residual, same layout as y, added after the activation
   // three-term operand form of the weights + per-row unscale (conv_h3_kernels.h), set by the ABI entries when the prepared buffer carries it
   const unsigned char* w3 = nullptr;
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(const Conv2dArgs a) {
         if (co >= a.CoutP) continue;
         float v = fmaf(acc[g][reg], a.scale[co], a.shift[co]);
         if (a.relu == 1) v = fmaxf(v, 0.f);
-        else if (a.relu == 2) v = gelu_erf_f(v);
+        else if (a.relu == 2) v = gelu_erf_f(v); else if (a.relu == 4) v = leaky_relu_f(v);
         const size_t oi = (size_t)co * oplane + po;
         if (a.res != nullptr) v += a.res[((size_t)n * a.out_ctotal + a.out_coff) * oplane + oi];
         if (a.relu == 3) v = fmaxf(v, 0.f);
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(const Conv2dArgs a) {
       const int co = gco / s2, sub = gco - co * s2, dy = sub / s, dx = sub - dy * s;
       float v = fmaf(acc[g][reg], a.scale[co], a.shift[co]);
       if (a.relu == 1) v = fmaxf(v, 0.f);
-      else if (a.relu == 2) v = gelu_erf_f(v);
+      else if (a.relu == 2) v = gelu_erf_f(v); else if (a.relu == 4) v = leaky_relu_f(v);
       const size_t oi = (size_t)co * oplane + (size_t)(oy * s + dy) * (a.Wo * s) + (ox * s + dx);
       if (a.res != nullptr) v += a.res[((size_t)n * a.out_ctotal + a.out_coff) * oplane + oi];
       if (a.relu == 3) v = fmaxf(v, 0.f);   // ReLU AFTER the residual add (ResNet BasicBlock)
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(256) void conv1x1_f16s_kernel(const Conv2dArgs a) {
         if (co >= a.CoutP) continue;
         float v = fmaf((t == 0 ? acc0[reg] : acc1[reg]) * unscale, a.scale[co], a.shift[co]);
         if (a.relu == 1) v = fmaxf(v, 0.f);
-        else if (a.relu == 2) v = gelu_erf_f(v);
+        else if (a.relu == 2) v = gelu_erf_f(v); else if (a.relu == 4) v = leaky_relu_f(v);
         const size_t oi = (size_t)co * HW + gp;
         if (rn != nullptr) v += rn[oi];
         if (a.relu == 3) v = fmaxf(v, 0.f);
@@ -390,7 +390,7 @@ __global__ __launch_bounds__(256) void conv1x1_f16s_kernel(const Conv2dArgs a) {
       const int co = gco / s2, sub = gco - co * s2, dy = sub / ups, dx = sub - dy * ups;
       float v = fmaf((t == 0 ? acc0[reg] : acc1[reg]) * unscale, a.scale[co], a.shift[co]);
       if (a.relu == 1) v = fmaxf(v, 0.f);
-      else if (a.relu == 2) v = gelu_erf_f(v);
+      else if (a.relu == 2) v = gelu_erf_f(v); else if (a.relu == 4) v = leaky_relu_f(v);
       const size_t oi = (size_t)co * oplane + (size_t)(oy * ups + dy) * (a.W * ups) + (ox * ups + dx);
       if (rn != nullptr) v += rn[oi];
       if (a.relu == 3) v = fmaxf(v, 0.f);
@@ -528,7 +528,7 @@ __global__ __launch_bounds__(256) void conv3x3_f16s_kernel(const Conv2dArgs a) {
     if (co >= a.CoutP) continue;
     float v = fmaf(acc[reg] * unscale, a.scale[co], a.shift[co]);
     if (a.relu == 1) v = fmaxf(v, 0.f);
-    else if (a.relu == 2) v = gelu_erf_f(v);
+    else if (a.relu == 2) v = gelu_erf_f(v); else if (a.relu == 4) v = leaky_relu_f(v);
     const size_t oi = (size_t)co * oplane + (size_t)oy * a.Wo + ox;
     if (a.res != nullptr) v += a.res[((size_t)n * a.out_ctotal + a.out_coff) * oplane + oi];
     if (a.relu == 3) v = fmaxf(v, 0.f);

@@ -26,6 +26,7 @@
                                // this unit stop matching the fusion kernels of gencomm_abi.hip bit for bit
 #include "voxel_batch_kernels.h"
 #include "voxel_kernels.h"
+#include "mpda_kernels.h"      // last: it sets `fp contract(off)` for itself and leaves `fast`, the state the headers above end in
 
 using namespace gc;
 
@@ -1183,6 +1184,37 @@ int gencomm_warp_weightfuse_fwd(const float* x, const float* score, const double
   GC_CHECK_ARG(B >= 1 && B <= 65535 && n >= B && C >= 1 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffll - 64, "weighted fuse: bad B/n/C/H/W");
   WeightFuseArgs a{x, score, theta, scene_off, out, C, H, W, 0};
   return warp_weightfuse_enqueue(a, B, (hipStream_t)stream);
+}
+
+// ---- MPDA's feature aligner (mpda_kernels.h)
+int gencomm_quad_attn_fwd(const float* q, const float* k, const float* v, const float* bias_table, float* out, int N, int Nkv, int heads,
+                          int dim_head, int H, int W, int q_ct, int kv_ct, int grid_mode, void* stream) {
+  GC_CHECK_ARG(q && k && v && out, "quad attention: null pointer (bias_table alone may be null)");
+  if (dim_head != 16 && dim_head != 32 && dim_head != 64) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "quad attention: unsupported dim_head %d (built: 16, 32, 64)", dim_head);
+    return fail(GC_ERR_ARG, msg);
+  }
+  GC_CHECK_ARG(H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "quad attention: H and W must be even and >= 2 (2 x 2 groups)");
+  GC_CHECK_ARG((long long)H * W <= 0x7fffffffll, "quad attention: the map has more than 2^31 - 1 pixels");
+  GC_CHECK_ARG(N >= 1 && N <= 65535 && heads >= 1 && heads <= 65535, "quad attention: 1..65535 query maps (N) and heads");
+  GC_CHECK_ARG(Nkv == N || Nkv == 1, "quad attention: Nkv must be N, or 1 (one key / value map for every query map)");
+  GC_CHECK_ARG(grid_mode == 0 || grid_mode == 1, "quad attention: grid_mode must be 0 (window) or 1 (grid)");
+  GC_CHECK_ARG((long long)heads * dim_head <= q_ct && (long long)heads * dim_head <= kv_ct,
+               "quad attention: q_ct / kv_ct (channels of one map of the q and of the k / v tensor) must be >= heads * dim_head");
+  GC_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) % 8 == 0, "quad attention: q, k, v and out must be 8-byte aligned");
+  QuadArgs a{q, k, v, bias_table, out, heads, H, W, q_ct, kv_ct, grid_mode, Nkv == 1 ? 1 : 0, 1.0f / sqrtf((float)dim_head)};
+  if (dim_head == 16) return quad_attn_launch<16>(a, N, (hipStream_t)stream);
+  if (dim_head == 32) return quad_attn_launch<32>(a, N, (hipStream_t)stream);
+  return quad_attn_launch<64>(a, N, (hipStream_t)stream);
+}
+
+int gencomm_resize_bilinear_fwd(const float* x, float* y, int N, int C, int Hi, int Wi, int Ho, int Wo, void* stream) {
+  GC_CHECK_ARG(x && y, "bilinear resize: null pointer");
+  GC_CHECK_ARG(N >= 1 && C >= 1 && Hi >= 1 && Wi >= 1 && Ho >= 1 && Wo >= 1, "bilinear resize: bad N/C/Hi/Wi/Ho/Wo");
+  GC_CHECK_ARG((long long)Hi * Wi <= 0x7fffffffll && (long long)Ho * Wo <= 0x7fffffffll - 256, "bilinear resize: a map has more than 2^31 - 1 pixels");
+  ResizeArgs a{x, y, Hi, Wi, Ho, Wo, (long long)N * C, 0.f, 0.f};
+  return resize_bilinear_enqueue(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

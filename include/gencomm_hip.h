@@ -356,7 +356,7 @@ int gencomm_conv2d_fwd(const float* x, const float* prepared, const float* scale
                        int N, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad, int relu,
                        int ups, int out_ctotal, int out_coff, void* stream);
 /* the same (no transposed-conv mode, whole-tensor output) with act in {0 none, 1 ReLU, 2 erf-GELU (nn.GELU), 3 ReLU applied after
- * the residual add (ResNet BasicBlock)} and an optional residual [N][Cout][Ho][Wo]: Linear + GELU, Linear + skip connection,
+ * the residual add (ResNet BasicBlock), 4 LeakyReLU with negative_slope 0.01 (nn.LeakyReLU(), before the residual add)} and an optional residual [N][Cout][Ho][Wo]: Linear + GELU, Linear + skip connection,
  * conv + BatchNorm + identity + ReLU in one launch */
 int gencomm_conv2d_act_res_fwd(const float* x, const float* prepared, const float* scale, const float* shift, const float* residual,
                                float* y, int N, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad, int act,
@@ -757,6 +757,31 @@ int gencomm_pyramid_score_fwd(const float* x, const float* weight, const float* 
                               int W, void* stream);
 int gencomm_warp_weightfuse_fwd(const float* x, const float* score, const double* theta, const int* scene_off, float* out, int B, int n, int C, int H,
                                 int W, void* stream);
+/* MPDA's feature aligner (opencood/models/mpda_modules/wg_fusion_modules.py, resizer.py; csrc/mpda_kernels.h; additive, ABI v12).  fp32 NCHW
+ * in, out and accumulation; every output element is stored exactly once, no atomics: two runs give the same bits.
+ *   gencomm_quad_attn_fwd      attention inside 2 x 2 groups, by index arithmetic on the maps (nothing is rearranged in memory).  With
+ *                              X = H / 2, Y = W / 2 and token t = 2 w1 + w2, group (x, y) holds the pixels (2 x + w1, 2 y + w2) for
+ *                              grid_mode 0 ('(x w1) (y w2)', window) and (w1 X + x, w2 Y + y) for grid_mode 1 ('(w1 x) (w2 y)', grid).
+ *                              Per query map n, head m and group: out = softmax(dim_head^-0.5 q k^T + bias) v over the 4 tokens, channel
+ *                              m dim_head + d of each tensor.  ARGUMENT FORM: three separate pointers, each AT ITS FIRST CHANNEL, plus the
+ *                              channel totals of the tensors they point into: q [N][q_ct][H][W], k and v [Nkv][kv_ct][H][W] (map n of q
+ *                              is q + n q_ct H W).  Cross attention (CrossAttention, :12-97): three tensors, q_ct = kv_ct = heads
+ *                              dim_head.  Self attention from one to_qkv output t [N][3 inner][H][W] (Attention, :101-174):
+ *                              q = t, k = t + inner H W, v = t + 2 inner H W, q_ct = kv_ct = 3 inner.  Nkv = N, or Nkv = 1: the one
+ *                              key / value map serves every query map (the reference's ego.repeat(n, 1, 1, 1)).  bias_table NULL (no
+ *                              bias) or [9][heads] = rel_pos_bias.weight at window_size 2, read at rel = (hi - hj + 1) 3 + (wi - wj + 1)
+ *                              for query token (hi, wi), key token (hj, wj): the module's rel_pos_indices buffer.  out
+ *                              [N][heads dim_head][H][W].  Domain: dim_head in {16, 32, 64}, heads 1..65535, N 1..65535, H and W even and
+ *                              >= 2, q_ct / kv_ct >= heads dim_head, all four pointers 8-byte aligned; anything else, and any null
+ *                              pointer but bias_table, returns a non-zero status without a launch and gencomm_last_error() names it.
+ *   gencomm_resize_bilinear_fwd  x [N][C][Hi][Wi] -> y [N][C][Ho][Wo] as F.interpolate(size=(Ho, Wo), mode='bilinear', align_corners=False)
+ *                              on torch's CPU arithmetic: source coordinate max((o + 0.5) (float)in / out - 0.5, 0), lower index
+ *                              truncated, upper neighbour clamped to the last row / column, columns interpolated inside each row
+ *                              first, then the two rows.  A weight of exactly 0 drops its term: Hi == Ho and Wi == Wo returns the
+ *                              input's bits. */
+int gencomm_quad_attn_fwd(const float* q, const float* k, const float* v, const float* bias_table, float* out, int N, int Nkv, int heads,
+                          int dim_head, int H, int W, int q_ct, int kv_ct, int grid_mode, void* stream);
+int gencomm_resize_bilinear_fwd(const float* x, float* y, int N, int C, int Hi, int Wi, int Ho, int Wo, void* stream);
 /* The adjoint of that block (csrc/convnext_bwd_kernels.h; additive, ABI v12).  Given the block's input x, dy and the parameters it writes
  * dx and, unless dx_only, the gradient of every parameter (d_gamma ignored where gamma is NULL); every output element is WRITTEN once, no
  * float atomics, parameter gradients are fixed-order sums of per-slab partials: two runs give the same bits.  u and h are recomputed per
