@@ -18,7 +18,7 @@ Public surface mirrors the reference's plugin API:
     Adapter(args), Reverter(args)      opencood/models/stamp_modules/adapter.py:759, :783 (STAMP's adapter / reverter; components, inference)
     PyramidFusion(model_cfg)           opencood/models/fuse_modules/pyramid_fuse.py:65 (HEAL's pyramid backbone + fusion; a component, inference)
     weighted_fuse(x, score, ...)       opencood/models/fuse_modules/pyramid_fuse.py:17
-    MPDAAlign(args)                    opencood/models/heter_model_baseline_w_mpda.py:232-262 (MPDA's feature aligner; a component, inference), with
+    MPDAAlign(args)                    opencood/models/heter_model_baseline_w_mpda.py:232-262 (MPDA's feature aligner; a component; trainable=True: training on mpda_bwd.py), with
     LearnableResizer, SwapFusionEncoder, CrossDomainFusionEncoder, DAImgHead   opencood/models/mpda_modules/
 
 All compute runs in hand-written HIP kernels behind the C ABI of ``include/gencomm_hip.h``.

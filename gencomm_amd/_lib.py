@@ -145,6 +145,12 @@ _SIGNATURES = {
     "gencomm_warp_weightfuse_fwd": (_i, [_p] * 5 + [_i] * 5 + [_p]),
     "gencomm_quad_attn_fwd": (_i, [_p] * 5 + [_i] * 9 + [_p]),
     "gencomm_resize_bilinear_fwd": (_i, [_p, _p] + [_i] * 6 + [_p]),
+    "gencomm_quad_attn_train_fwd": (_i, [_p] * 5 + [C.c_float, _p] + [_i] * 9 + [_p]),
+    "gencomm_quad_attn_bwd_workspace_bytes": (_ll, [_i] * 7),
+    "gencomm_quad_attn_bwd": (_i, [_p] * 5 + [C.c_float] + [_p] * 5 + [_i] * 9 + [_p, _ll, _p]),
+    "gencomm_resize_bilinear_bwd": (_i, [_p, _p] + [_i] * 6 + [_p]),
+    "gencomm_leaky_relu_fwd": (_i, [_p, _p, _ll, C.c_float, _p]),
+    "gencomm_leaky_relu_bwd": (_i, [_p, _p, _p, _ll, C.c_float, _p]),
     "gencomm_iou3d_pairwise_fwd": (_i, [_p, _i, _p, _i, _i, _p, _p]),
     "gencomm_iou3d_max_boxes": (_i, []),
     "gencomm_iou3d_nms_workspace_bytes": (_ll, [_i]),

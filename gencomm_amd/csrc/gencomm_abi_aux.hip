@@ -27,6 +27,7 @@
 #include "voxel_batch_kernels.h"
 #include "voxel_kernels.h"
 #include "mpda_kernels.h"      // last: it sets `fp contract(off)` for itself and leaves `fast`, the state the headers above end in
+#include "mpda_bwd_kernels.h"  // after mpda_kernels.h (QuadTokens, resize_source); the same contract discipline
 
 using namespace gc;
 
@@ -1215,6 +1216,115 @@ int gencomm_resize_bilinear_fwd(const float* x, float* y, int N, int C, int Hi, 
   GC_CHECK_ARG((long long)Hi * Wi <= 0x7fffffffll && (long long)Ho * Wo <= 0x7fffffffll - 256, "bilinear resize: a map has more than 2^31 - 1 pixels");
   ResizeArgs a{x, y, Hi, Wi, Ho, Wo, (long long)N * C, 0.f, 0.f};
   return resize_bilinear_enqueue(a, (hipStream_t)stream);
+}
+
+// ---- MPDA training (mpda_bwd_kernels.h)
+static int quad_domain(const char* what, int N, int Nkv, int heads, int dim_head, int H, int W, int q_ct, int kv_ct, int grid_mode) {
+  char msg[160];
+  if (dim_head != 16 && dim_head != 32 && dim_head != 64) {
+    snprintf(msg, sizeof msg, "%s: unsupported dim_head %d (built: 16, 32, 64)", what, dim_head);
+    return fail(GC_ERR_ARG, msg);
+  }
+  const char* bad = nullptr;
+  if (!(H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0)) bad = "H and W must be even and >= 2 (2 x 2 groups)";
+  else if ((long long)H * W > 0x7fffffffll) bad = "the map has more than 2^31 - 1 pixels";
+  else if (!(N >= 1 && N <= 65535 && heads >= 1 && heads <= 65535)) bad = "1..65535 query maps (N) and heads";
+  else if (!(Nkv == N || Nkv == 1)) bad = "Nkv must be N, or 1 (one key / value map for every query map)";
+  else if (!(grid_mode == 0 || grid_mode == 1)) bad = "grid_mode must be 0 (window) or 1 (grid)";
+  else if (!((long long)heads * dim_head <= q_ct && (long long)heads * dim_head <= kv_ct))
+    bad = "q_ct / kv_ct (channels of one map of the q and of the k / v tensor) must be >= heads * dim_head";
+  if (bad == nullptr) return GC_OK;
+  snprintf(msg, sizeof msg, "%s: %s", what, bad);
+  return fail(GC_ERR_ARG, msg);
+}
+
+int gencomm_quad_attn_train_fwd(const float* q, const float* k, const float* v, const float* bias_table, const unsigned short* keep, float keep_scale,
+                                float* out, int N, int Nkv, int heads, int dim_head, int H, int W, int q_ct, int kv_ct, int grid_mode, void* stream) {
+  GC_CHECK_ARG(q && k && v && out, "quad attention train: null pointer (bias_table and keep alone may be null)");
+  if (int rc = quad_domain("quad attention train", N, Nkv, heads, dim_head, H, W, q_ct, kv_ct, grid_mode)) return rc;
+  GC_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) % 8 == 0, "quad attention train: q, k, v and out must be 8-byte aligned");
+  GC_CHECK_ARG((uintptr_t)keep % 2 == 0, "quad attention train: keep must be 2-byte aligned");
+  QuadTrainArgs a{{q, k, v, bias_table, out, heads, H, W, q_ct, kv_ct, grid_mode, Nkv == 1 ? 1 : 0, 1.0f / sqrtf((float)dim_head)}, keep, keep_scale};
+  if (dim_head == 16) return quad_attn_train_launch<16>(a, N, (hipStream_t)stream);
+  if (dim_head == 32) return quad_attn_train_launch<32>(a, N, (hipStream_t)stream);
+  return quad_attn_train_launch<64>(a, N, (hipStream_t)stream);
+}
+
+// workspace: [2][N][heads dim_head][H][W] floats of per-map dk | dv slabs where one key / value map serves N > 1 query maps, then
+// [N ceil(X Y / 64)][heads][9] floats of per-workgroup partials of the table's gradient where there is a table
+static long long quad_bwd_slab_floats(int N, int Nkv, int heads, int dim_head, int H, int W) {
+  return (Nkv == 1 && N > 1) ? 2ll * N * heads * dim_head * H * W : 0ll;
+}
+
+long long gencomm_quad_attn_bwd_workspace_bytes(int N, int Nkv, int heads, int dim_head, int H, int W, int has_bias) {
+  if (quad_domain("quad attention backward", N, Nkv, heads, dim_head, H, W, heads * dim_head, heads * dim_head, 0)) return -1;
+  const long long wgs = (long long)N * (((H / 2) * (W / 2) + kQuadGroups - 1) / kQuadGroups);
+  return (long long)align_up((size_t)(quad_bwd_slab_floats(N, Nkv, heads, dim_head, H, W) + (has_bias ? wgs * heads * 9 : 0)) * sizeof(float), 256);
+}
+
+int gencomm_quad_attn_bwd(const float* q, const float* k, const float* v, const float* bias_table, const unsigned short* keep, float keep_scale,
+                          const float* dout, float* dq, float* dk, float* dv, float* dbias, int N, int Nkv, int heads, int dim_head, int H, int W,
+                          int q_ct, int kv_ct, int grid_mode, void* workspace, long long workspace_bytes, void* stream) {
+  GC_CHECK_ARG(q && k && v && dout && dq && dk && dv, "quad attention backward: null pointer (bias_table, dbias, keep and an empty workspace alone may be null)");
+  GC_CHECK_ARG(bias_table == nullptr || dbias != nullptr, "quad attention backward: null pointer (dbias with a bias_table)");
+  if (int rc = quad_domain("quad attention backward", N, Nkv, heads, dim_head, H, W, q_ct, kv_ct, grid_mode)) return rc;
+  GC_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)workspace) % 8 == 0,
+               "quad attention backward: q, k, v, dout, dq, dk, dv and the workspace must be 8-byte aligned");
+  GC_CHECK_ARG((uintptr_t)keep % 2 == 0, "quad attention backward: keep must be 2-byte aligned");
+  const long long need = gencomm_quad_attn_bwd_workspace_bytes(N, Nkv, heads, dim_head, H, W, bias_table != nullptr);
+  if (need > 0 && (workspace == nullptr || workspace_bytes < need))
+    return fail(GC_ERR_WORKSPACE, "quad attention backward: workspace too small (gencomm_quad_attn_bwd_workspace_bytes)");
+  hipStream_t st = (hipStream_t)stream;
+  const long long slab = quad_bwd_slab_floats(N, Nkv, heads, dim_head, H, W);
+  const long long count = (long long)heads * dim_head * H * W;
+  GC_CHECK_ARG((count + 255) / 256 <= 0x7fffffffll, "quad attention backward: heads * dim_head * H * W too large");
+  float* ws = reinterpret_cast<float*>(workspace);
+  float* part = bias_table != nullptr ? ws + slab : nullptr;
+  QuadBwdArgs a{q, k, v, bias_table, dout, keep, dq, dk, dv, part, heads, H, W, q_ct, kv_ct, kv_ct, grid_mode, Nkv == 1 ? 1 : 0,
+                1.0f / sqrtf((float)dim_head), keep_scale};
+  if (slab) { a.dk = ws; a.dv = ws + slab / 2; a.dkv_ct = heads * dim_head; }
+  int rc = dim_head == 16 ? quad_attn_bwd_launch<16>(a, N, st) : dim_head == 32 ? quad_attn_bwd_launch<32>(a, N, st) : quad_attn_bwd_launch<64>(a, N, st);
+  if (rc) return rc;
+  if (slab) {
+    GC_KLOG("quad_kv_reduce_kernel");
+    quad_kv_reduce_kernel<<<dim3((unsigned)((count + 255) / 256), 2), 256, 0, st>>>(ws, dk, dv, N, count);
+  }
+  if (part != nullptr) {
+    const int P = N * (((H / 2) * (W / 2) + kQuadGroups - 1) / kQuadGroups);
+    GC_KLOG("quad_dbias_reduce_kernel");
+    quad_dbias_reduce_kernel<<<dim3(9, heads), 64, 0, st>>>(part, dbias, P, heads);
+  }
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_resize_bilinear_bwd(const float* dy, float* dx, int N, int C, int Hi, int Wi, int Ho, int Wo, void* stream) {
+  GC_CHECK_ARG(dy && dx, "bilinear resize backward: null pointer");
+  GC_CHECK_ARG(N >= 1 && C >= 1 && Hi >= 1 && Wi >= 1 && Ho >= 1 && Wo >= 1, "bilinear resize backward: bad N/C/Hi/Wi/Ho/Wo");
+  GC_CHECK_ARG((long long)Hi * Wi <= 0x7fffffffll - 256 && (long long)Ho * Wo <= 0x7fffffffll,
+               "bilinear resize backward: a map has more than 2^31 - 1 pixels");
+  ResizeBwdArgs a{dy, dx, Hi, Wi, Ho, Wo, (long long)N * C, 0.f, 0.f};
+  return resize_bilinear_bwd_enqueue(a, (hipStream_t)stream);
+}
+
+static unsigned ew_blocks(long long n) { return (unsigned)std::min<long long>((n + 255) / 256, 1 << 20); }
+
+int gencomm_leaky_relu_fwd(const float* x, float* y, long long n, float slope, void* stream) {
+  GC_CHECK_ARG(x && y, "leaky relu: null pointer");
+  GC_CHECK_ARG(n >= 1, "leaky relu: n must be >= 1");
+  GC_KLOG("leaky_relu_fwd_kernel");
+  leaky_relu_fwd_kernel<<<ew_blocks(n), 256, 0, (hipStream_t)stream>>>(x, y, n, slope);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_leaky_relu_bwd(const float* y, const float* dy, float* dx, long long n, float slope, void* stream) {
+  GC_CHECK_ARG(y && dy && dx, "leaky relu backward: null pointer");
+  GC_CHECK_ARG(n >= 1, "leaky relu backward: n must be >= 1");
+  GC_KLOG("leaky_relu_bwd_kernel");
+  leaky_relu_bwd_kernel<<<ew_blocks(n), 256, 0, (hipStream_t)stream>>>(y, dy, dx, n, slope);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
 }
 
 }  // extern "C"

@@ -16,8 +16,12 @@ The ``torch.nn`` classes are parameter containers; every forward runs on the HIP
   F.interpolate(bilinear)        gencomm_resize_bilinear_fwd
   residual_block                 conv3x3 + folded BatchNorm + LeakyReLU(0.01) (act 4), conv3x3 + folded BatchNorm + the block's skip
 
-Inference only: ``train()`` mode, and a grad-enabled call with a trainable parameter or input, raise ``NotImplementedError`` naming
-``mpda training`` (no backward kernels; dropout and BatchNorm batch statistics are not built). ``wg_att.window_size`` other than 2 and
+The default constructors infer only: ``train()`` mode, and a grad-enabled call with a trainable parameter or input, raise
+``NotImplementedError`` naming ``mpda training``. ``trainable=True`` (on ``MPDAAlign``, ``LearnableResizer``, ``SwapFusionEncoder``,
+``CrossDomainFusionEncoder`` and ``DAImgHead``, passed down to children; no parameter or buffer is added, the ``state_dict`` is the
+same) sends those calls through the ``torch.autograd.Function``s of ``mpda_bwd.py``: the same kernel calls with a tape, the attention
+through ``gencomm_quad_attn_train_fwd``, dropout and BatchNorm batch statistics in ``train()`` mode, and the HIP backward. A
+``no_grad`` call in ``eval()`` mode runs the inference path on a trainable module too. ``wg_att.window_size`` other than 2 and
 odd H or W raise naming the key / the dimension. ``CrossDomainSwapFusionBlock`` hard-codes ``win_size = 2`` whatever the yaml's
 ``window_size`` says, as the reference does."""
 from __future__ import annotations
@@ -42,6 +46,19 @@ def _refuse_training(module: nn.Module, what: str, tensors) -> None:
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [*tensors, *module.parameters()]):
         raise NotImplementedError(f"{what}: mpda training is not built (no backward kernels): call it under torch.no_grad(), or with "
                                   "nothing that requires a gradient")
+
+
+def _training_path(module: nn.Module, what: str, tensors) -> bool:
+    """True: the call goes through mpda_bwd.py (a trainable module in train() mode, or with gradients to produce). False: inference;
+    a default module refuses what it cannot do, in the words it always used."""
+    if getattr(module, "trainable", False):
+        if module.training:
+            return True
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [*tensors, *module.parameters()]):
+            return True
+        return False
+    _refuse_training(module, what, tensors)
+    return False
 
 
 def _check_even(what: str, H: int, W: int) -> None:
@@ -71,6 +88,103 @@ def quad_attention(q, k, v, bias_table, heads: int, dim_head: int, grid_mode: in
                                                 N, Nkv, heads, dim_head, H, W, q_ct, kv_ct, int(grid_mode),
                                                 stream_ptr(q.device)), "gencomm_quad_attn_fwd")
     return out
+
+
+def pack_keep(keep):
+    """bool [N, heads, G, 16] (element 4 i + j: probability (query token i, key token j) survives) -> the kernel's packed words
+    [N, heads, G], bit 4 i + j, as int16 holding the uint16 bit pattern."""
+    w = (keep.to(torch.int32) << torch.arange(16, dtype=torch.int32, device=keep.device)).sum(dim=-1)
+    return torch.where(w >= 32768, w - 65536, w).to(torch.int16).contiguous()
+
+
+def draw_keep(masks, N: int, heads: int, G: int, p: float, device):
+    """The attention's keep mask, bool [N, heads, G, 16], drawn as ``torch.rand(N, heads, G, 16, device=device) >= p`` at its position
+    in the order of a ``v2xvit_bwd._Masks`` (recorded there as the bool tensor; replayed from it)."""
+    if masks.replay:
+        keep = masks.recorded[masks.pos]
+        masks.pos += 1
+    else:
+        keep = torch.rand(N, heads, G, 16, device=device) >= p
+        masks.recorded.append(keep)
+    return keep
+
+
+def unpack_keep(words):
+    """The inverse of pack_keep: int16 [N, heads, G] -> bool [N, heads, G, 16]."""
+    w = words.to(torch.int32) & 0xFFFF
+    return ((w[..., None] >> torch.arange(16, dtype=torch.int32, device=words.device)) & 1).bool()
+
+
+def quad_attention_train(q, k, v, bias_table, heads: int, dim_head: int, grid_mode: int, q_coff: int = 0, k_coff: int = 0, v_coff: int = 0,
+                         keep=None, keep_scale: float = 1.0):
+    """``gencomm_quad_attn_train_fwd``: ``quad_attention`` with an optional packed keep mask (``pack_keep``) on the probabilities."""
+    N, q_ct, H, W = q.shape
+    Nkv, kv_ct = k.shape[:2]
+    if tuple(v.shape) != tuple(k.shape) or tuple(k.shape[2:]) != (H, W):
+        raise ValueError(f"quad_attention_train: k {tuple(k.shape)} and v {tuple(v.shape)} must agree and share the queries' {H}x{W} map")
+    inner, hw = heads * dim_head, H * W
+    if max(k_coff, v_coff) + inner > kv_ct or q_coff + inner > q_ct:
+        raise ValueError("quad_attention_train: channel offset + heads dim_head exceeds the tensor's channels")
+    if keep is not None and (keep.dtype != torch.int16 or tuple(keep.shape) != (N, heads, (H // 2) * (W // 2)) or not keep.is_contiguous()):
+        raise ValueError(f"quad_attention_train: keep must be contiguous int16 [{N}, {heads}, {(H // 2) * (W // 2)}]")
+    out = torch.empty(N, inner, H, W, dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().gencomm_quad_attn_train_fwd(ptr(q) + 4 * q_coff * hw, ptr(k) + 4 * k_coff * hw, ptr(v) + 4 * v_coff * hw, ptr(bias_table),
+                                                      ptr(keep), float(keep_scale), ptr(out), N, Nkv, heads, dim_head, H, W, q_ct, kv_ct,
+                                                      int(grid_mode), stream_ptr(q.device)), "gencomm_quad_attn_train_fwd")
+    return out
+
+
+def quad_attention_bwd(q, k, v, bias_table, dout, heads: int, dim_head: int, grid_mode: int, q_coff: int = 0, k_coff: int = 0, v_coff: int = 0,
+                       keep=None, keep_scale: float = 1.0, self_form: bool = False):
+    """``gencomm_quad_attn_bwd`` -> (dq, dk, dv, dbias or None). ``self_form``: q, k and v are one to_qkv output [N, 3 inner, H, W] and
+    dq | dk | dv come back as ONE tensor dqkv of that shape (returned three times)."""
+    N, q_ct, H, W = q.shape
+    Nkv, kv_ct = k.shape[:2]
+    inner, hw, dev = heads * dim_head, H * W, q.device
+    if max(k_coff, v_coff) + inner > kv_ct or q_coff + inner > q_ct:
+        raise ValueError("quad_attention_bwd: channel offset + heads dim_head exceeds the tensor's channels")
+    if tuple(dout.shape) != (N, inner, H, W):
+        raise ValueError(f"quad_attention_bwd: dout {tuple(dout.shape)} must be [{N}, {inner}, {H}, {W}]")
+    l = _lib.lib()
+    if self_form:
+        dq = dk = dv = torch.empty_like(q) if q_ct == 3 * inner else torch.zeros_like(q)
+    else:
+        dq = torch.empty_like(q) if q_ct == inner else torch.zeros_like(q)
+        dk, dv = (torch.empty_like(k) if kv_ct == inner else torch.zeros_like(k) for _ in range(2))
+    dbias = torch.empty(9, heads, dtype=torch.float32, device=dev) if bias_table is not None else None
+    need = _lib.check_size(l.gencomm_quad_attn_bwd_workspace_bytes(N, Nkv, heads, dim_head, H, W, int(bias_table is not None)),
+                           "gencomm_quad_attn_bwd_workspace_bytes")
+    ws = torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
+    _lib.check(l.gencomm_quad_attn_bwd(ptr(q) + 4 * q_coff * hw, ptr(k) + 4 * k_coff * hw, ptr(v) + 4 * v_coff * hw, ptr(bias_table), ptr(keep),
+                                       float(keep_scale), ptr(dout), ptr(dq) + 4 * q_coff * hw, ptr(dk) + 4 * k_coff * hw, ptr(dv) + 4 * v_coff * hw,
+                                       ptr(dbias), N, Nkv, heads, dim_head, H, W, q_ct, kv_ct, int(grid_mode), ptr(ws), need, stream_ptr(dev)),
+               "gencomm_quad_attn_bwd")
+    return dq, dk, dv, dbias
+
+
+def resize_bilinear_bwd(dy, in_size):
+    """The adjoint of ``resize_bilinear``: dy [n, C, Ho, Wo] -> dx [n, C, Hi, Wi] (``gencomm_resize_bilinear_bwd``, a gather)."""
+    dy = f32c(dy)
+    n, C, Ho, Wo = dy.shape
+    Hi, Wi = int(in_size[0]), int(in_size[1])
+    dx = torch.empty(n, C, Hi, Wi, dtype=torch.float32, device=dy.device)
+    _lib.check(_lib.lib().gencomm_resize_bilinear_bwd(ptr(dy), ptr(dx), n, C, Hi, Wi, Ho, Wo, stream_ptr(dy.device)), "gencomm_resize_bilinear_bwd")
+    return dx
+
+
+def leaky_relu(x, slope: float = 0.01):
+    x = f32c(x)
+    y = torch.empty_like(x)
+    _lib.check(_lib.lib().gencomm_leaky_relu_fwd(ptr(x), ptr(y), x.numel(), float(slope), stream_ptr(x.device)), "gencomm_leaky_relu_fwd")
+    return y
+
+
+def leaky_relu_bwd(y, dy, slope: float = 0.01):
+    """dx = dy (y > 0 ? 1 : slope), from the OUTPUT y; slope 0 is the ReLU's adjoint."""
+    y, dy = f32c(y), f32c(dy)
+    dx = torch.empty_like(y)
+    _lib.check(_lib.lib().gencomm_leaky_relu_bwd(ptr(y), ptr(dy), ptr(dx), y.numel(), float(slope), stream_ptr(y.device)), "gencomm_leaky_relu_bwd")
+    return dx
 
 
 def resize_bilinear(x, size):
@@ -158,8 +272,9 @@ class SwapFusionBlock(nn.Module):  # wg_fusion_modules.py:177-206
 
 
 class SwapFusionEncoder(nn.Module):  # wg_fusion_modules.py:341-376 (unmasked)
-    def __init__(self, args):
+    def __init__(self, args, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.depth = args["depth"]
         input_dim, mlp_dim, dim_head = args["input_dim"], args["mlp_dim"], args["dim_head"]
         window_size, drop_out = args["window_size"], args["drop_out"]
@@ -174,65 +289,129 @@ class SwapFusionEncoder(nn.Module):  # wg_fusion_modules.py:341-376 (unmasked)
         self.mlp_head = nn.Sequential(nn.Identity(), nn.LayerNorm(input_dim), nn.Linear(input_dim, input_dim), nn.Identity())
         self._linears = _LinearCache()
 
-    def _attention(self, key, pre: PreNormResidual, h, grid_mode):
+    def _attention(self, key, pre: PreNormResidual, h, grid_mode, tape=None, masks=None):
+        """With a `tape` (training) the attention goes through gencomm_quad_attn_train_fwd and the tape receives what the backward
+        reads; the packed keep mask of the probabilities is drawn FIRST in the half-block, then the mask after to_out."""
         att, cache = pre.fn, self._linears
         qkv = _linear(_ln(h, pre.norm), cache.get((key, "qkv"), [att.to_qkv.weight], lambda: (att.to_qkv.weight, None), h.device))
         inner = att.heads * att.dim_head
-        out = quad_attention(qkv, qkv, qkv, f32c(att.rel_pos_bias.weight.detach()), att.heads, att.dim_head, grid_mode, 0, inner, 2 * inner)
+        table = f32c(att.rel_pos_bias.weight.detach())
         o = att.to_out[0]
-        return _linear(out, cache.get((key, "out"), [o.weight], lambda: (o.weight, None), h.device), 0, h)
+        entry = cache.get((key, "out"), [o.weight], lambda: (o.weight, None), h.device)
+        if tape is None:
+            out = quad_attention(qkv, qkv, qkv, table, att.heads, att.dim_head, grid_mode, 0, inner, 2 * inner)
+            return _linear(out, entry, 0, h)
+        p_att, p_out = float(att.attend[1].p), float(att.to_out[1].p)
+        keep, ks = None, 1.0
+        if masks.active and p_att > 0:
+            n, _, H, W = h.shape
+            keep, ks = pack_keep(draw_keep(masks, n, att.heads, (H // 2) * (W // 2), p_att, h.device)), 1.0 / (1.0 - p_att)
+        out = quad_attention_train(qkv, qkv, qkv, table, att.heads, att.dim_head, grid_mode, 0, inner, 2 * inner, keep, ks)
+        if masks.active and p_out > 0:
+            y, m = masks.apply(_linear(out, entry), p_out)
+            y = y + h
+        else:
+            y, m = _linear(out, entry, 0, h), None
+        tape.append(("att", pre, int(grid_mode), h, qkv, out, table, keep, ks, m))
+        return y
 
-    def _feed_forward(self, key, pre: PreNormResidual, h):
+    def _feed_forward(self, key, pre: PreNormResidual, h, tape=None, masks=None):
         cache, l0, l3 = self._linears, pre.fn.net[0], pre.fn.net[3]
         mid = _linear(_ln(h, pre.norm), cache.get((key, "ff0"), [l0.weight, l0.bias], lambda: (l0.weight, l0.bias), h.device), 2)   # Linear + GELU
-        return _linear(mid, cache.get((key, "ff3"), [l3.weight, l3.bias], lambda: (l3.weight, l3.bias), h.device), 0, h)           # Linear + skip
+        e3 = cache.get((key, "ff3"), [l3.weight, l3.bias], lambda: (l3.weight, l3.bias), h.device)
+        if tape is None:
+            return _linear(mid, e3, 0, h)                                                                                          # Linear + skip
+        p = float(pre.fn.net[2].p)
+        if masks.active and p > 0:
+            mid, m_mid = masks.apply(mid, p)
+            y, m_out = masks.apply(_linear(mid, e3), p)
+            y = y + h
+        else:
+            y, m_mid, m_out = _linear(mid, e3, 0, h), None, None
+        tape.append(("ff", pre, h, mid, m_mid, m_out))
+        return y
+
+    def dropout_p(self) -> float:
+        return max([float(m.p) for m in self.modules() if isinstance(m, nn.Dropout)], default=0.0)
+
+    def _forward_hip(self, x, tape=None, masks=None):
+        """`tape` (a list) and `masks` (v2xvit_bwd._Masks): the training forward of mpda_bwd.SwapEncoderFunction. The kernel calls are
+        the same; with dropout active the epilogue-fused residuals become separate additions."""
+        h = f32c(x)
+        for i, blk in enumerate(self.layers):
+            b = blk.block
+            h = self._attention((i, "window"), b[1], h, 0, tape, masks)
+            h = self._feed_forward((i, "window"), b[2], h, tape, masks)
+            h = self._attention((i, "grid"), b[5], h, 1, tape, masks)
+            h = self._feed_forward((i, "grid"), b[6], h, tape, masks)
+        if tape is not None:
+            tape.append(("head", h))
+        return _head(self._linears, self.mlp_head, h)
 
     def forward(self, x, mask=None):
         if mask is not None:
             raise NotImplementedError("SwapFusionEncoder: a mask is not built (the reference's module ignores it: self.mask = False)")
-        _refuse_training(self, "SwapFusionEncoder", [x])
+        train = _training_path(self, "SwapFusionEncoder", [x])
         n, C, H, W = x.shape
         if C != self.mlp_head[1].normalized_shape[0]:
             raise ValueError(f"SwapFusionEncoder: input has {C} channels, the module was built with input_dim {self.mlp_head[1].normalized_shape[0]}")
         _check_even("SwapFusionEncoder", H, W)
         require_gpu(x, "SwapFusionEncoder.forward")
+        if train:
+            from .mpda_bwd import SwapEncoderFunction
+            return SwapEncoderFunction.apply(self, x, *self.parameters())
         with torch.no_grad():
-            h = f32c(x)
-            for i, blk in enumerate(self.layers):
-                b = blk.block
-                h = self._attention((i, "window"), b[1], h, 0)
-                h = self._feed_forward((i, "window"), b[2], h)
-                h = self._attention((i, "grid"), b[5], h, 1)
-                h = self._feed_forward((i, "grid"), b[6], h)
-            return _head(self._linears, self.mlp_head, h)
+            return self._forward_hip(x)
 
 
 # ----------------------------------------------------------------------------------------- the resizer
 class residual_block(nn.Module):  # resizer.py:11-24
-    def __init__(self, input_dim):
+    def __init__(self, input_dim, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.module = nn.Sequential(nn.Conv2d(input_dim, input_dim, 3, padding=1), nn.BatchNorm2d(input_dim), nn.LeakyReLU(),
                                     nn.Conv2d(input_dim, input_dim, 3, padding=1), nn.BatchNorm2d(input_dim))
 
     def forward(self, x):
+        """Called by LearnableResizer (which has refused what a default module refuses): the folded inference layers, or, for a
+        trainable block in train() mode or with gradients to produce, mpda_bwd.ResidualBlockFunction."""
+        if self.trainable and (self.training or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))):
+            from .mpda_bwd import ResidualBlockFunction
+            return ResidualBlockFunction.apply(self, x, *self.parameters())
         m = self.module
         return _conv_bn_act(_conv_bn_act(x, m[0], m[1], 4), m[3], m[4], 0, residual=x)
 
 
 class LearnableResizer(nn.Module):  # resizer.py:27-72
-    def __init__(self, args):
+    def __init__(self, args, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.channel_selector = nn.Conv2d(args["input_channel"], args["output_channel"], 1)
-        self.wg_att_1 = SwapFusionEncoder(args["wg_att"])
-        self.wg_att_2 = SwapFusionEncoder(args["wg_att"])
-        self.res_blocks = nn.ModuleList([residual_block(args["residual"]["input_dim"]) for _ in range(args["residual"]["depth"])])
+        self.wg_att_1 = SwapFusionEncoder(args["wg_att"], trainable)
+        self.wg_att_2 = SwapFusionEncoder(args["wg_att"], trainable)
+        self.res_blocks = nn.ModuleList([residual_block(args["residual"]["input_dim"], trainable) for _ in range(args["residual"]["depth"])])
+
+    def _forward_train(self, ego_feature, cav_feature):
+        """The same calls as the inference path, each an autograd node of its own (mpda_bwd.py; the 1x1 channel_selector through
+        conv2d_hip's own HIP backward); the additions are plain torch, as in the inference path."""
+        from .mpda_bwd import ResizeFunction
+        size = tuple(ego_feature.shape[2:])
+        cav = conv2d_hip(f32c(cav_feature), self.channel_selector, None, relu=False)
+        one = ResizeFunction.apply(self.wg_att_1(cav), size)
+        two = one
+        for blk in self.res_blocks:
+            two = blk(two)
+        two = self.wg_att_2(two + one)
+        return ResizeFunction.apply(cav, size) + two
 
     def forward(self, ego_feature, cav_feature):
-        _refuse_training(self, "LearnableResizer", [ego_feature, cav_feature])
+        train = _training_path(self, "LearnableResizer", [ego_feature, cav_feature])
         h, w = ego_feature.shape[2:]
         _check_even("LearnableResizer (the ego's map)", h, w)
         _check_even("LearnableResizer (the collaborator's map)", *cav_feature.shape[2:])
         require_gpu(cav_feature, "LearnableResizer.forward")
+        if train:
+            return self._forward_train(ego_feature, cav_feature)
         with torch.no_grad():
             cav = conv2d_hip(f32c(cav_feature), self.channel_selector, None, relu=False)
             one = resize_bilinear(self.wg_att_1(cav), (h, w))
@@ -269,8 +448,9 @@ class CrossDomainSwapFusionBlock(nn.Module):  # wg_fusion_modules.py:209-303
 
 
 class CrossDomainFusionEncoder(nn.Module):  # wg_fusion_modules.py:306-338
-    def __init__(self, args):
+    def __init__(self, args, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.depth = args["depth"]
         input_dim, heads, dim_head, window_size = args["input_dim"], args["heads"], args["dim_head"], args["window_size"]
         _check_dim_head("CrossDomainFusionEncoder", dim_head)
@@ -282,23 +462,43 @@ class CrossDomainFusionEncoder(nn.Module):  # wg_fusion_modules.py:306-338
         lin = seq[1]
         return _linear(_ln(x, seq[0]), self._linears.get(key, [lin.weight, lin.bias], lambda: (lin.weight, lin.bias), x.device))
 
-    def _cross(self, key, att: CrossAttention, query, ego, grid_mode):
+    def _cross(self, key, att: CrossAttention, query, ego, grid_mode, tape=None):
         q = self._project((key, "q"), att.to_q, query)
         k = self._project((key, "k"), att.to_k, ego)       # the ego's n_ego maps (1: broadcast to every query map by the kernel)
         v = self._project((key, "v"), att.to_v, ego)
-        a = quad_attention(q, k, v, None, att.heads, att.dim_head, grid_mode)
+        if tape is None:
+            a = quad_attention(q, k, v, None, att.heads, att.dim_head, grid_mode)
+        else:
+            a = quad_attention_train(q, k, v, None, att.heads, att.dim_head, grid_mode)     # no dropout in the reference's CrossAttention
+            tape.append(("cross", att, int(grid_mode), query, q, k, v, a))
         p = att.proj
         return _linear(a, self._linears.get((key, "proj"), [p.weight, p.bias], lambda: (p.weight, p.bias), query.device), 0, query)   # + skip
 
-    def _mlp(self, key, norm, mlp, x):
+    def _mlp(self, key, norm, mlp, x, tape=None):
         cache, l0, l2 = self._linears, mlp[0], mlp[2]
         mid = _linear(_ln(x, norm), cache.get((key, "0"), [l0.weight, l0.bias], lambda: (l0.weight, l0.bias), x.device), 2)
+        if tape is not None:
+            tape.append(("mlp", norm, mlp, x, mid))
         return _linear(mid, cache.get((key, "2"), [l2.weight, l2.bias], lambda: (l2.weight, l2.bias), x.device), 0, x)
+
+    def _forward_hip(self, ego_feature, cav_feature, tape=None):
+        ego, x = f32c(ego_feature), f32c(cav_feature)
+        for i, blk in enumerate(self.layers):
+            x = self._cross((i, "win"), blk.cross_win_1, x, ego, 0, tape)
+            x = self._mlp((i, "mlp_1"), blk.prenorm1, blk.mlp_1, x, tape)
+            x = self._cross((i, "grid"), blk.cross_win_2, x, ego, 1, tape)
+            x = self._mlp((i, "mlp_2"), blk.prenorm2, blk.mlp_2, x, tape)
+            if tape is not None:
+                tape.append(("ln", blk.post_norm, x))
+            x = _ln(x, blk.post_norm)
+        if tape is not None:
+            tape.append(("head", x))
+        return _head(self._linears, self.mlp_head, x)
 
     def forward(self, ego_feature, cav_feature):
         """ego_feature [n, C, H, W] or [1, C, H, W] (one ego map for every collaborator: what the reference builds with
         ``ego.repeat(n, 1, 1, 1)``), cav_feature [n, C, H, W] -> [n, C, H, W]."""
-        _refuse_training(self, "CrossDomainFusionEncoder", [ego_feature, cav_feature])
+        train = _training_path(self, "CrossDomainFusionEncoder", [ego_feature, cav_feature])
         n, C, H, W = cav_feature.shape
         if ego_feature.shape[0] not in (1, n) or tuple(ego_feature.shape[1:]) != (C, H, W):
             raise ValueError(f"CrossDomainFusionEncoder: ego_feature {tuple(ego_feature.shape)} must be [{n} or 1, {C}, {H}, {W}]")
@@ -307,15 +507,11 @@ class CrossDomainFusionEncoder(nn.Module):  # wg_fusion_modules.py:306-338
                              f"{self.mlp_head[1].normalized_shape[0]}")
         _check_even("CrossDomainFusionEncoder", H, W)
         require_gpu(cav_feature, "CrossDomainFusionEncoder.forward")
+        if train:
+            from .mpda_bwd import CrossDomainFunction
+            return CrossDomainFunction.apply(self, ego_feature, cav_feature, *self.parameters())
         with torch.no_grad():
-            ego, x = f32c(ego_feature), f32c(cav_feature)
-            for i, blk in enumerate(self.layers):
-                x = self._cross((i, "win"), blk.cross_win_1, x, ego, 0)
-                x = self._mlp((i, "mlp_1"), blk.prenorm1, blk.mlp_1, x)
-                x = self._cross((i, "grid"), blk.cross_win_2, x, ego, 1)
-                x = self._mlp((i, "mlp_2"), blk.prenorm2, blk.mlp_2, x)
-                x = _ln(x, blk.post_norm)
-            return _head(self._linears, self.mlp_head, x)
+            return self._forward_hip(ego_feature, cav_feature)
 
 
 # ----------------------------------------------------------------------------------------- the classifier and the aligner
@@ -326,8 +522,9 @@ class GradientScalarLayer(nn.Module):  # gradient_layer.py: the identity in the 
 
 
 class DAImgHead(nn.Module):  # classfier.py:36-65
-    def __init__(self, in_channels):
+    def __init__(self, in_channels, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.conv1_da = nn.Conv2d(in_channels, 512, kernel_size=1, stride=1)
         self.conv2_da = nn.Conv2d(512, 1, kernel_size=1, stride=1)
         self.rgl = GradientScalarLayer(-9.1)
@@ -336,8 +533,11 @@ class DAImgHead(nn.Module):  # classfier.py:36-65
             torch.nn.init.constant_(l.bias, 0)
 
     def forward(self, x):
-        _refuse_training(self, "DAImgHead", [x])
+        train = _training_path(self, "DAImgHead", [x])
         require_gpu(x, "DAImgHead.forward")
+        if train:
+            from .mpda_bwd import DAHeadFunction
+            return DAHeadFunction.apply(self, x, *self.parameters())
         with torch.no_grad():
             return conv2d_hip(conv2d_hip(f32c(x), self.conv1_da, None, relu=True), self.conv2_da, None, relu=False)
 
@@ -348,15 +548,34 @@ class MPDAAlign(nn.Module):
     then ``cdt`` (``rebuttal: true``: unchanged); the classifier sees the scene's aligned maps. For an ego-only scene the reference
     computes the resizer and ``cdt`` and discards the result: that work is skipped here, the outputs are the same."""
 
-    def __init__(self, args):
+    def __init__(self, args, trainable=False):
         super().__init__()
-        self.resizer = LearnableResizer(args["resizer"])
-        self.cdt = CrossDomainFusionEncoder(args["cdt"])
-        self.classifier = DAImgHead(args["classifier"]) if "classifier" in args else DAImgHead(128)
+        self.trainable = bool(trainable)
+        self.resizer = LearnableResizer(args["resizer"], trainable)
+        self.cdt = CrossDomainFusionEncoder(args["cdt"], trainable)
+        self.classifier = DAImgHead(args["classifier"] if "classifier" in args else 128, trainable)
         self.rebuttal = args.get("rebuttal", False)
 
+    def _forward_train(self, x, lens):
+        """`aligned` assembled with autograd-visible ops (slices and one torch.cat). `rebuttal: true` passes the maps, and so the
+        gradients, straight through. An ego-only scene skips the resizer and cdt as the inference path does: no gradient is lost (the
+        reference discards that branch), but the resizer's BatchNorm running statistics do not see the ego-to-ego call the reference
+        makes in train() mode (a stated difference)."""
+        if self.rebuttal or max(lens) == 1:
+            aligned = x.clone()
+        else:
+            parts, off = [], 0
+            for k in lens:
+                ego = x[off:off + 1]
+                parts.append(ego)
+                if k > 1:
+                    parts.append(self.cdt(ego, self.resizer(ego, x[off + 1:off + k])))
+                off += k
+            aligned = torch.cat(parts, dim=0)
+        return aligned, self.classifier(aligned)
+
     def forward(self, heter_feature_2d, record_len):
-        _refuse_training(self, "MPDAAlign", [heter_feature_2d])
+        train = _training_path(self, "MPDAAlign", [heter_feature_2d])
         lens = record_len_list(record_len)
         n = heter_feature_2d.shape[0]
         if sum(lens) != n or min(lens) < 1:
@@ -364,6 +583,8 @@ class MPDAAlign(nn.Module):
         if not self.rebuttal and max(lens) > 1:
             _check_even("MPDAAlign", *heter_feature_2d.shape[2:])
         require_gpu(heter_feature_2d, "MPDAAlign.forward")
+        if train:
+            return self._forward_train(f32c(heter_feature_2d), lens)
         with torch.no_grad():
             x = f32c(heter_feature_2d)
             if self.rebuttal or max(lens) == 1:

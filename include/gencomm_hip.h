@@ -782,6 +782,34 @@ int gencomm_warp_weightfuse_fwd(const float* x, const float* score, const double
 int gencomm_quad_attn_fwd(const float* q, const float* k, const float* v, const float* bias_table, float* out, int N, int Nkv, int heads,
                           int dim_head, int H, int W, int q_ct, int kv_ct, int grid_mode, void* stream);
 int gencomm_resize_bilinear_fwd(const float* x, float* y, int N, int C, int Hi, int Wi, int Ho, int Wo, void* stream);
+/* MPDA training (csrc/mpda_bwd_kernels.h; additive, ABI v12).  No float atomics: two runs give the same bits in every output.
+ *   gencomm_quad_attn_train_fwd  gencomm_quad_attn_fwd plus dropout on the 4 x 4 probabilities.  keep [N][heads][X Y] uint16, one word per
+ *                              group (group index x Y + y): bit 4 i + j set = probability (query token i, key token j) survives and is
+ *                              multiplied by keep_scale = 1 / (1 - p), clear = 0.  keep NULL (keep_scale ignored), or all 16 bits set with
+ *                              keep_scale 1, gives gencomm_quad_attn_fwd's bits.  Nothing else is saved for the backward.
+ *   gencomm_quad_attn_bwd      the adjoint, from q, k, v, bias_table, keep / keep_scale (as given to the forward) and dout
+ *                              [N][heads dim_head][H][W]; the scores are recomputed.  dq is written in q's form ([N][q_ct][H][W] at the
+ *                              first query channel), dk and dv in k's and v's ([Nkv][kv_ct][H][W]): in the self form dq | dk | dv are the
+ *                              channel blocks of one dqkv [N][3 inner][H][W].  Only the heads dim_head channels from each pointer on are
+ *                              written, each element once.  Nkv = 1 with N > 1: dk / dv are the sums over the N query maps, added in map
+ *                              order from per-map slabs in the workspace.  dbias [9][heads] = sum over maps and groups of dS at rel(i, j),
+ *                              per-workgroup partials (workspace) added in a fixed order; bias_table NULL: dbias may be NULL and is not
+ *                              written.  Domain as gencomm_quad_attn_fwd, all seven float pointers and the workspace 8-byte aligned;
+ *                              status 2 for a workspace smaller than gencomm_quad_attn_bwd_workspace_bytes (-1 outside the domain; 0
+ *                              bytes needs no workspace pointer).
+ *   gencomm_resize_bilinear_bwd  the adjoint of gencomm_resize_bilinear_fwd as a gather per source pixel: dy [N][C][Ho][Wo] -> dx
+ *                              [N][C][Hi][Wi], every element written once, with the forward's own weights.  Hi == Ho and Wi == Wo
+ *                              returns dy's bits.
+ *   gencomm_leaky_relu_fwd / _bwd  y = x > 0 ? x : slope x over n floats; dx = y > 0 ? dy : slope dy, from the OUTPUT y. */
+int gencomm_quad_attn_train_fwd(const float* q, const float* k, const float* v, const float* bias_table, const unsigned short* keep, float keep_scale,
+                                float* out, int N, int Nkv, int heads, int dim_head, int H, int W, int q_ct, int kv_ct, int grid_mode, void* stream);
+long long gencomm_quad_attn_bwd_workspace_bytes(int N, int Nkv, int heads, int dim_head, int H, int W, int has_bias);
+int gencomm_quad_attn_bwd(const float* q, const float* k, const float* v, const float* bias_table, const unsigned short* keep, float keep_scale,
+                          const float* dout, float* dq, float* dk, float* dv, float* dbias, int N, int Nkv, int heads, int dim_head, int H, int W,
+                          int q_ct, int kv_ct, int grid_mode, void* workspace, long long workspace_bytes, void* stream);
+int gencomm_resize_bilinear_bwd(const float* dy, float* dx, int N, int C, int Hi, int Wi, int Ho, int Wo, void* stream);
+int gencomm_leaky_relu_fwd(const float* x, float* y, long long n, float slope, void* stream);
+int gencomm_leaky_relu_bwd(const float* y, const float* dy, float* dx, long long n, float slope, void* stream);
 /* The adjoint of that block (csrc/convnext_bwd_kernels.h; additive, ABI v12).  Given the block's input x, dy and the parameters it writes
  * dx and, unless dx_only, the gradient of every parameter (d_gamma ignored where gamma is NULL); every output element is WRITTEN once, no
  * float atomics, parameter gradients are fixed-order sums of per-slab partials: two runs give the same bits.  u and h are recomputed per
