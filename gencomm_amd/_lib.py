@@ -143,6 +143,14 @@ _SIGNATURES = {
     "gencomm_gconv3x3_fwd": (_i, [_p] * 5 + [_i] * 7 + [_p]),
     "gencomm_pyramid_score_fwd": (_i, [_p] * 6 + [_i] * 4 + [_p]),
     "gencomm_warp_weightfuse_fwd": (_i, [_p] * 5 + [_i] * 5 + [_p]),
+    "gencomm_gconv3x3_prepare_t": (_i, [_p, _p, _i, _p]),
+    "gencomm_gconv3x3_dgrad": (_i, [_p] * 6 + [_i] * 6 + [_p]),
+    "gencomm_gconv3x3_wgrad_fixed_scratch_floats": (_ll, [_i] * 5),
+    "gencomm_gconv3x3_wgrad_fixed": (_i, [_p] * 3 + [_i] * 6 + [_p, _ll, _p]),
+    "gencomm_pyramid_score_bwd_scratch_floats": (_ll, [_i] * 4),
+    "gencomm_pyramid_score_bwd": (_i, [_p] * 9 + [_i] * 4 + [_p, _ll, _p]),
+    "gencomm_warp_weightfuse_bwd_scratch_floats": (_ll, [_i] * 3),
+    "gencomm_warp_weightfuse_bwd": (_i, [_p] * 8 + [_ll] + [_i] * 5 + [_p]),
     "gencomm_quad_attn_fwd": (_i, [_p] * 5 + [_i] * 9 + [_p]),
     "gencomm_resize_bilinear_fwd": (_i, [_p, _p] + [_i] * 6 + [_p]),
     "gencomm_quad_attn_train_fwd": (_i, [_p] * 5 + [C.c_float, _p] + [_i] * 9 + [_p]),

@@ -373,15 +373,26 @@ def gconv3x3_check(conv: nn.Module) -> int:
     return cpg
 
 
-def gconv3x3_hip(x: torch.Tensor, conv: nn.Conv2d, bn: Optional[nn.BatchNorm2d] = None, relu: bool = False) -> torch.Tensor:
-    """act(BN_eval(conv(x))) for the grouped 3x3 of the ResNeXt ``Bottleneck`` as one launch of ``gencomm_gconv3x3_fwd``: the same
-    per-module cache of the prepared weight and the folded BatchNorm as ``conv2d_hip``. Inference only: batch statistics and
-    gradients through this layer are not built and raise."""
+def gconv3x3_hip(x: torch.Tensor, conv: nn.Conv2d, bn: Optional[nn.BatchNorm2d] = None, relu: bool = False,
+                 trainable: bool = False) -> torch.Tensor:
+    """act(BN(conv(x))) for the grouped 3x3 of the ResNeXt ``Bottleneck`` as one launch of ``gencomm_gconv3x3_fwd``: the same
+    per-module cache of the prepared weight and the folded BatchNorm as ``conv2d_hip``. By default inference only: batch statistics and
+    gradients through this layer raise. ``trainable=True`` opts in to both (``pyramid_bwd.GconvEvalFn`` / ``GconvBnTrainFn``, chosen by
+    ``bn_batch_statistics(bn)`` as ``conv2d_hip`` chooses); under ``no_grad`` with eval-mode BatchNorm it is the launch below."""
     cpg = gconv3x3_check(conv)
     params = [p for p in (conv.weight, conv.bias) + ((bn.weight, bn.bias) if bn is not None else ()) if p is not None]
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+    grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+    stats = bn is not None and bn_batch_statistics(bn)
+    if trainable:
+        require_gpu(x, "gconv3x3_hip")
+        if conv.bias is not None:
+            raise NotImplementedError("grouped convolution: training a layer with a conv bias is not built (no layer of the pyramid has one)")
+        if grad or stats:
+            from .pyramid_bwd import gconv3x3_train
+            return gconv3x3_train(x, conv, bn, relu, cpg, grad, stats)
+    if grad:
         raise NotImplementedError("grouped convolution: the backward is not built (pyramid training is a later change)")
-    if bn is not None and bn_batch_statistics(bn):
+    if stats:
         raise NotImplementedError("grouped convolution: BatchNorm batch statistics (train() mode) are not built")
     require_gpu(x, "gconv3x3_hip")
     x = f32c(x)

@@ -42,6 +42,7 @@ class BasicBlock(nn.Module):  # resblock.py:18-64
 
 class Bottleneck(nn.Module):  # resblock.py:67-122, with the expansion 1 that PyramidFusion sets on the reference's class (pyramid_fuse.py:72)
     expansion = 1
+    trainable = False   # PyramidFusion(trainable=True) sets it on its blocks: the grouped 3x3 may then take gradients / batch statistics
 
     def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64):
         super().__init__()
@@ -62,7 +63,7 @@ class Bottleneck(nn.Module):  # resblock.py:67-122, with the expansion 1 that Py
         if self.conv2.groups == 1:
             out = conv2d_hip(out, self.conv2, self.bn2, relu=True)
         else:
-            out = gconv3x3_hip(out, self.conv2, self.bn2, relu=True)                    # the grouped 3x3: gencomm_gconv3x3_fwd
+            out = gconv3x3_hip(out, self.conv2, self.bn2, relu=True, trainable=self.trainable)   # the grouped 3x3: gencomm_gconv3x3_fwd
         return conv2d_hip(out, self.conv3, self.bn3, relu=True, residual=identity)      # relu(bn3(conv3(out)) + identity)
 
 

@@ -76,14 +76,10 @@ constexpr int FUSE_KM = 12;
 // Every output pixel p whose bilinear cell (agent transform th) contains the source pixel (qx, qy), with its tap weight: f(p, wgt).
 // Candidates = a window around q's pre-image (float64); each candidate's sampling position is fuse_point's, as in the forward.
 // Shared by the gather passes of the attention backward and of the max backward.
+// The matches among the candidates [x_lo, x_hi] x [y_lo, y_hi] (inside the map), row by row.
 template <class F>
-__device__ __forceinline__ void fuse_for_each_match(const double* __restrict__ th, int qx, int qy, int H, int W, F&& f) {
-  const double gx = fuse_base(qx, W), gy = fuse_base(qy, H);
-  const double det = th[0] * th[4] - th[1] * th[3];
-  const double xb = (th[4] * (gx - th[2]) - th[1] * (gy - th[5])) / det, yb = (-th[3] * (gx - th[2]) + th[0] * (gy - th[5])) / det;
-  const double pxf = ((xb + 1.0) * W - 1.0) * 0.5, pyf = ((yb + 1.0) * H - 1.0) * 0.5;
-  const int x_lo = max((int)floor(pxf - 1.6), 0), x_hi = min((int)ceil(pxf + 1.6), W - 1);
-  const int y_lo = max((int)floor(pyf - 1.6), 0), y_hi = min((int)ceil(pyf + 1.6), H - 1);
+__device__ __forceinline__ void fuse_for_each_match_in(const double* __restrict__ th, int qx, int qy, int H, int W, int x_lo, int x_hi, int y_lo,
+                                                       int y_hi, F&& f) {
   for (int py = y_lo; py <= y_hi; ++py)
     for (int px = x_lo; px <= x_hi; ++px) {
       int x0, y0;
@@ -95,6 +91,39 @@ __device__ __forceinline__ void fuse_for_each_match(const double* __restrict__ t
       if (wgt == 0.f) continue;
       f(py * W + px, wgt);
     }
+}
+
+template <class F>
+__device__ __forceinline__ void fuse_for_each_match(const double* __restrict__ th, int qx, int qy, int H, int W, F&& f) {
+  const double gx = fuse_base(qx, W), gy = fuse_base(qy, H);
+  const double det = th[0] * th[4] - th[1] * th[3];
+  const double xb = (th[4] * (gx - th[2]) - th[1] * (gy - th[5])) / det, yb = (-th[3] * (gx - th[2]) + th[0] * (gy - th[5])) / det;
+  const double pxf = ((xb + 1.0) * W - 1.0) * 0.5, pyf = ((yb + 1.0) * H - 1.0) * 0.5;
+  const int x_lo = max((int)floor(pxf - 1.6), 0), x_hi = min((int)ceil(pxf + 1.6), W - 1);
+  const int y_lo = max((int)floor(pyf - 1.6), 0), y_hi = min((int)ceil(pyf + 1.6), H - 1);
+  fuse_for_each_match_in(th, qx, qy, H, W, x_lo, x_hi, y_lo, y_hi, f);
+}
+
+// The same for ANY transform: the candidates are the bounding box of the pre-image of the 2 x 2 cell around (qx, qy), from the L1 row norms
+// of the inverse map in pixel units (the quantity fuse_bwd_plan_kernel bounds by 1.5 for a tame transform); the whole map where the
+// transform is singular.  Slow where the map shrinks an agent much, exact, and without atomics.
+template <class F>
+__device__ __forceinline__ void fuse_for_each_match_wide(const double* __restrict__ th, int qx, int qy, int H, int W, F&& f) {
+  int x_lo = 0, x_hi = W - 1, y_lo = 0, y_hi = H - 1;
+  const double det = th[0] * th[4] - th[1] * th[3];
+  if (fabs(det) > 1e-12 && fabs(det) < 1e12) {
+    const double gx = fuse_base(qx, W), gy = fuse_base(qy, H);
+    const double xb = (th[4] * (gx - th[2]) - th[1] * (gy - th[5])) / det, yb = (-th[3] * (gx - th[2]) + th[0] * (gy - th[5])) / det;
+    const double pxf = ((xb + 1.0) * W - 1.0) * 0.5, pyf = ((yb + 1.0) * H - 1.0) * 0.5;
+    const double m00 = th[0], m01 = th[1] * W / H, m10 = th[3] * H / W, m11 = th[4];   // det of this matrix == det
+    const double hx = (fabs(m11) + fabs(m01)) / fabs(det) * 1.001 + 0.6, hy = (fabs(m10) + fabs(m00)) / fabs(det) * 1.001 + 0.6;
+    const double xl = floor(pxf - hx), xh = ceil(pxf + hx), yl = floor(pyf - hy), yh = ceil(pyf + hy);
+    if (xl == xl && xh == xh && yl == yl && yh == yh) {   // clamped as doubles: the conversions below stay in range
+      x_lo = (int)fmin(fmax(xl, 0.0), (double)W); x_hi = (int)fmax(fmin(xh, (double)(W - 1)), -1.0);
+      y_lo = (int)fmin(fmax(yl, 0.0), (double)H); y_hi = (int)fmax(fmin(yh, (double)(H - 1)), -1.0);
+    }
+  }
+  fuse_for_each_match_in(th, qx, qy, H, W, x_lo, x_hi, y_lo, y_hi, f);
 }
 
 }  // namespace gc

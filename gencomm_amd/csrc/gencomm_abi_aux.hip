@@ -24,6 +24,7 @@
 #include "pyramid_kernels.h"   // out of alphabetical order on purpose: fuse_cell.h must first be parsed where v2v_kernels.h includes it (the
                                // headers between iou3d_kernels.h and swap_attn_bwd_kernels.h run under `fp contract(off)`), or the warp kernels of
                                // this unit stop matching the fusion kernels of gencomm_abi.hip bit for bit
+#include "pyramid_bwd_kernels.h"   // directly behind pyramid_kernels.h: the same contract state, so the recomputed shares are the forward's
 #include "voxel_batch_kernels.h"
 #include "voxel_kernels.h"
 #include "mpda_kernels.h"      // last: it sets `fp contract(off)` for itself and leaves `fast`, the state the headers above end in
@@ -1325,6 +1326,89 @@ int gencomm_leaky_relu_bwd(const float* y, const float* dy, float* dx, long long
   leaky_relu_bwd_kernel<<<ew_blocks(n), 256, 0, (hipStream_t)stream>>>(y, dy, dx, n, slope);
   GC_HIP(hipGetLastError());
   return GC_OK;
+}
+
+// ---- HEAL's PyramidFusion, training (pyramid_bwd_kernels.h)
+int gencomm_gconv3x3_prepare_t(const float* weight, float* packed, int cpg, void* stream) {
+  if (int rc = gconv_check(1, 32 * cpg, cpg, 1, 1, 1)) return rc;
+  GC_CHECK_ARG(weight && packed, "grouped 3x3 prepare (transposed): null pointer");
+  const int total = 32 * cpg * cpg * 9;
+  gconv3x3_pack_t_kernel<<<(total + 255) / 256, 256, 0, (hipStream_t)stream>>>(weight, packed, cpg);
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
+int gencomm_gconv3x3_dgrad(const float* dy, const float* packed_t, const float* unit_scale, const float* zero_shift, float* dx, float* spread, int n,
+                           int C, int cpg, int H, int W, int stride, void* stream) {
+  if (int rc = gconv_check(n, C, cpg, H, W, stride)) return rc;
+  GC_CHECK_ARG(dy && packed_t && unit_scale && zero_shift && dx, "grouped 3x3 dgrad: null pointer");
+  GC_CHECK_ARG(stride == 1 || spread != nullptr, "grouped 3x3 dgrad: stride 2 needs the spread buffer (n C H W floats)");
+  GC_CHECK_ARG(dx != dy && dx != spread, "grouped 3x3 dgrad: dx must not alias dy or the spread buffer (neighbouring tiles read the halo)");
+  hipStream_t st = (hipStream_t)stream;
+  const float* src = dy;
+  if (stride == 2) {
+    const long long maps = (long long)n * C, total = maps * H * W;
+    gconv3x3_spread_kernel<<<(unsigned)std::min<long long>((total + 255) / 256, 1 << 20), 256, 0, st>>>(dy, spread, maps, H, W, (H - 1) / 2 + 1,
+                                                                                                         (W - 1) / 2 + 1);
+    src = spread;
+  }
+  return gconv3x3_enqueue(src, packed_t, unit_scale, zero_shift, dx, n, cpg, H, W, 1, 0, st);
+}
+
+long long gencomm_gconv3x3_wgrad_fixed_scratch_floats(int n, int cpg, int H, int W, int stride) {
+  if (gconv_check(n, 32 * cpg, cpg, H, W, stride)) return -1;
+  return (long long)gconv3x3_wgrad_plan(n, cpg, H, W, stride).slabs * 32 * 9 * cpg * cpg;
+}
+
+int gencomm_gconv3x3_wgrad_fixed(const float* x, const float* dy, float* dw, int n, int C, int cpg, int H, int W, int stride, float* scratch,
+                                 long long scratch_floats, void* stream) {
+  if (int rc = gconv_check(n, C, cpg, H, W, stride)) return rc;
+  GC_CHECK_ARG(x && dy && dw && scratch, "grouped 3x3 wgrad: null pointer");
+  GC_CHECK_ARG(gconv3x3_wgrad_plan(n, cpg, H, W, stride).total_tiles <= 0x7fffffffll, "grouped 3x3 wgrad: more than 2^31 - 1 tiles");
+  if (scratch_floats < gencomm_gconv3x3_wgrad_fixed_scratch_floats(n, cpg, H, W, stride))
+    return fail(GC_ERR_WORKSPACE, "grouped 3x3 wgrad: scratch too small (gencomm_gconv3x3_wgrad_fixed_scratch_floats)");
+  return gconv3x3_wgrad_enqueue(x, dy, dw, scratch, n, cpg, H, W, stride, (hipStream_t)stream);
+}
+
+long long gencomm_pyramid_score_bwd_scratch_floats(int n, int C, int H, int W) {
+  if (!(n >= 1 && n <= 65535 && C >= 1 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffll - 64)) {
+    fail(GC_ERR_ARG, "pyramid score backward: bad n/C/H/W");
+    return -1;
+  }
+  return (long long)pyramid_score_bwd_scratch_floats(n, C, H, W);
+}
+
+int gencomm_pyramid_score_bwd(const float* x, const float* weight, const float* occ, const int* rect, const float* d_occ, const float* d_score,
+                              float* dx, float* dw, float* db, int n, int C, int H, int W, float* scratch, long long scratch_floats, void* stream) {
+  GC_CHECK_ARG(x && weight && occ, "pyramid score backward: null pointer (x, weight, occ)");
+  GC_CHECK_ARG(d_occ || d_score, "pyramid score backward: d_occ and d_score are both null");
+  GC_CHECK_ARG(dx || dw, "pyramid score backward: nothing to compute (dx and dw are both null)");
+  GC_CHECK_ARG((dw == nullptr) == (db == nullptr), "pyramid score backward: dw and db come together");
+  const long long need = gencomm_pyramid_score_bwd_scratch_floats(n, C, H, W);
+  if (need < 0) return GC_ERR_ARG;
+  if (dw != nullptr && (scratch == nullptr || scratch_floats < need))
+    return fail(GC_ERR_WORKSPACE, "pyramid score backward: scratch too small (gencomm_pyramid_score_bwd_scratch_floats)");
+  PyrScoreBwdArgs a{x, weight, occ, rect, d_occ, d_score, dx, nullptr, C, H, W};
+  return pyramid_score_bwd_enqueue(a, dw, db, scratch, n, (hipStream_t)stream);
+}
+
+long long gencomm_warp_weightfuse_bwd_scratch_floats(int n, int H, int W) {
+  if (!(n >= 1 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffll - 128)) {
+    fail(GC_ERR_ARG, "weighted fuse backward: bad n/H/W");
+    return -1;
+  }
+  return (long long)warp_weightfuse_bwd_scratch_floats(n, H, W);
+}
+
+int gencomm_warp_weightfuse_bwd(const float* x, const float* score, const double* theta, const int* scene_off, const float* dout, float* dx,
+                                float* dscore, float* scratch, long long scratch_floats, int B, int n, int C, int H, int W, void* stream) {
+  GC_CHECK_ARG(x && score && theta && scene_off && dout && dx && dscore && scratch, "weighted fuse backward: null pointer");
+  GC_CHECK_ARG(B >= 1 && B <= 65535 && n >= B && n <= 65535 && C >= 1 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffll - 128,
+               "weighted fuse backward: bad B/n/C/H/W");
+  if (scratch_floats < (long long)warp_weightfuse_bwd_scratch_floats(n, H, W))
+    return fail(GC_ERR_WORKSPACE, "weighted fuse backward: scratch too small (gencomm_warp_weightfuse_bwd_scratch_floats)");
+  WeightFuseBwdArgs a{x, score, theta, scene_off, dout, dx, dscore, nullptr, nullptr, C, H, W, 0};
+  return warp_weightfuse_bwd_enqueue(a, scratch, B, n, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -9,9 +9,11 @@ Per level ``forward_collab`` is two launches: ``gencomm_pyramid_score_fwd`` (hea
 ``[N, C, H, W]`` maps of the reference are never written). The grouped 3x3 runs on ``gencomm_gconv3x3_fwd``
 (``bev_backbone.gconv3x3_hip``), everything else of the backbone on ``conv2d_hip``.
 
-Inference only: the module refuses ``train()`` mode and grad-enabled calls with anything trainable (pyramid training -- backward
-kernels and BatchNorm batch statistics through the grouped layer -- is not built), and ``align_corners: true``, which no shipped
-yaml sets."""
+By default inference only: the module refuses ``train()`` mode and grad-enabled calls with anything trainable, and always
+``align_corners: true``, which no shipped yaml sets. Training is opt-in, as for every other component: ``PyramidFusion(cfg,
+trainable=True)``, ``weighted_fuse(..., trainable=True)``, ``score_head(..., trainable=True)`` go through ``pyramid_bwd.py`` (HIP
+backward kernels, BatchNorm batch statistics through the grouped layer); under ``no_grad`` in ``eval()`` such a module takes the
+inference launches below and returns the same bits."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
@@ -68,12 +70,13 @@ def _refuse_training(what, tensors):
                                   "or with nothing that requires a gradient")
 
 
-def weighted_fuse(x, score, record_len, affine_matrix, align_corners=False):
+def weighted_fuse(x, score, record_len, affine_matrix, align_corners=False, trainable=False):
     """pyramid_fuse.py:17-63 as one launch of ``gencomm_warp_weightfuse_fwd``: x [sum(n_cav), C, H, W], score [sum(n_cav), 1, H, W],
-    affine_matrix [B, L, L, 2, 3] -> [B, C, H, W]."""
+    affine_matrix [B, L, L, 2, 3] -> [B, C, H, W]. ``trainable=True``: differentiable in x and score (``pyramid_bwd.WeightedFuseFn``)."""
     if align_corners:
         raise NotImplementedError("weighted_fuse: align_corners=True is not built (no shipped yaml sets it)")
-    _refuse_training("weighted_fuse", (x, score))
+    if not trainable:
+        _refuse_training("weighted_fuse", (x, score))
     require_gpu(x, "weighted_fuse")
     lens = record_len_list(record_len)
     n, C, H, W = x.shape
@@ -83,15 +86,19 @@ def weighted_fuse(x, score, record_len, affine_matrix, align_corners=False):
         raise ValueError(f"weighted_fuse: score must be [{n}, 1, {H}, {W}], got {tuple(score.shape)}")
     x, score = f32c(x), f32c(score)
     theta = gather_ego_thetas(affine_matrix, lens).to(x.device)
+    if trainable and torch.is_grad_enabled() and (x.requires_grad or score.requires_grad):
+        from .pyramid_bwd import WeightedFuseFn
+        return WeightedFuseFn.apply(x, score, theta, dev_ints(off, x.device), B)
     out = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().gencomm_warp_weightfuse_fwd(ptr(x), ptr(score), ptr(theta), ptr(dev_ints(off, x.device)), ptr(out), B, n, C, H, W,
                                                       stream_ptr(x.device)), "gencomm_warp_weightfuse_fwd")
     return out
 
 
-def score_head(x: torch.Tensor, head: nn.Conv2d, rects: Optional[Sequence[Sequence[int]]] = None):
+def score_head(x: torch.Tensor, head: nn.Conv2d, rects: Optional[Sequence[Sequence[int]]] = None, trainable: bool = False):
     """(occ_map, score) of one level, both [n, 1, H, W], as one launch of ``gencomm_pyramid_score_fwd``: occ = head(x),
-    score = (sigmoid(occ) + 1e-4) * crop mask. ``rects``: one (h0, h1, w0, w1) per agent (``crop_rects``), or None for no mask."""
+    score = (sigmoid(occ) + 1e-4) * crop mask. ``rects``: one (h0, h1, w0, w1) per agent (``crop_rects``), or None for no mask.
+    ``trainable=True``: both outputs are differentiable in x and the head's parameters (``pyramid_bwd.ScoreHeadFn``)."""
     require_gpu(x, "score_head")
     x = f32c(x)
     n, C, H, W = x.shape
@@ -102,6 +109,9 @@ def score_head(x: torch.Tensor, head: nn.Conv2d, rects: Optional[Sequence[Sequen
         if len(rects) != n:
             raise ValueError(f"score_head: {len(rects)} rectangles for {n} agents")
         rect = dev_ints([v for r in rects for v in r], x.device)
+    if trainable and torch.is_grad_enabled() and (x.requires_grad or head.weight.requires_grad or head.bias.requires_grad):
+        from .pyramid_bwd import ScoreHeadFn
+        return ScoreHeadFn.apply(x, rect, head.weight, head.bias)
     occ = torch.empty((n, 1, H, W), dtype=torch.float32, device=x.device)
     score = torch.empty_like(occ)
     _lib.check(_lib.lib().gencomm_pyramid_score_fwd(ptr(x), ptr(f32c(head.weight.detach())), ptr(f32c(head.bias.detach())), ptr(rect), ptr(occ),
@@ -110,8 +120,9 @@ def score_head(x: torch.Tensor, head: nn.Conv2d, rects: Optional[Sequence[Sequen
 
 
 class PyramidFusion(ResNetBEVBackbone):  # pyramid_fuse.py:65-168
-    def __init__(self, model_cfg, input_channels=64):
+    def __init__(self, model_cfg, input_channels=64, trainable=False):
         super().__init__(model_cfg, input_channels)
+        self.trainable = bool(trainable)   # a plain attribute, like the one set on the blocks below: the state_dict keys do not change
         if model_cfg["resnext"]:
             self.resnet = ResNetModified(Bottleneck, self.model_cfg['layer_nums'], self.model_cfg['layer_strides'], self.model_cfg['num_filters'],
                                          inplanes=model_cfg.get('inplanes', 64), groups=32, width_per_group=4)
@@ -120,8 +131,13 @@ class PyramidFusion(ResNetBEVBackbone):  # pyramid_fuse.py:65-168
             raise NotImplementedError("PyramidFusion: align_corners: true is not built (no shipped yaml sets it)")
         for i in range(self.num_levels):   # the single supervision heads
             setattr(self, f"single_head_{i}", nn.Conv2d(self.model_cfg["num_filters"][i], 1, kernel_size=1))
+        for m in self.modules():
+            if isinstance(m, Bottleneck):
+                m.trainable = self.trainable
 
     def _refuse(self, spatial_features):
+        if self.trainable:
+            return
         if self.training:
             raise NotImplementedError("PyramidFusion: train() mode is not built (BatchNorm batch statistics through the grouped layer; pyramid "
                                       "training is a later change): call .eval()")
@@ -131,14 +147,14 @@ class PyramidFusion(ResNetBEVBackbone):  # pyramid_fuse.py:65-168
         """The single-agent pass: (final_feature, occ_map_list)."""
         self._refuse(spatial_features)
         feature_list = self.get_multiscale_feature(spatial_features)
-        occ_map_list = [score_head(feature_list[i], getattr(self, f"single_head_{i}"))[0] for i in range(self.num_levels)]
+        occ_map_list = [score_head(feature_list[i], getattr(self, f"single_head_{i}"), None, self.trainable)[0] for i in range(self.num_levels)]
         return self.decode_multiscale_feature(feature_list), occ_map_list
 
     def forward_collab(self, spatial_features, record_len, affine_matrix, agent_modality_list=None, cam_crop_info=None):
         """spatial_features [sum(record_len), C, H, W], affine_matrix [B, L, L, 2, 3], agent_modality_list: the modality of each cav,
         cam_crop_info: {'m2': {'crop_ratio_W_m2': 0.5, 'crop_ratio_H_m2': 0.5}} -> (fused_feature, occ_map_list)."""
         self._refuse(spatial_features)
-        crop = cam_crop_info is not None and len(cam_crop_info) > 0
+        crop = cam_crop_info is not None and len(cam_crop_info) > 0 and not self.training   # the reference skips the mask when self.training
         if crop and (agent_modality_list is None or len(agent_modality_list) != spatial_features.shape[0]):
             raise ValueError("PyramidFusion.forward_collab: cam_crop_info needs agent_modality_list with one entry per agent")
         feature_list = self.get_multiscale_feature(spatial_features)
@@ -146,7 +162,7 @@ class PyramidFusion(ResNetBEVBackbone):  # pyramid_fuse.py:65-168
         for i in range(self.num_levels):
             H, W = feature_list[i].shape[2:]
             rects = crop_rects(H, W, agent_modality_list, cam_crop_info) if crop else None
-            occ_map, score = score_head(feature_list[i], getattr(self, f"single_head_{i}"), rects)
+            occ_map, score = score_head(feature_list[i], getattr(self, f"single_head_{i}"), rects, self.trainable)
             occ_map_list.append(occ_map)
-            fused_feature_list.append(weighted_fuse(feature_list[i], score, record_len, affine_matrix, self.align_corners))
+            fused_feature_list.append(weighted_fuse(feature_list[i], score, record_len, affine_matrix, self.align_corners, self.trainable))
         return self.decode_multiscale_feature(fused_feature_list), occ_map_list

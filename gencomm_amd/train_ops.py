@@ -213,6 +213,10 @@ def bn_train_update(bn):
             momentum = 1.0 / float(bn.num_batches_tracked)
         elif bn.num_batches_tracked is not None and bn.num_batches_tracked.is_cuda and bn.num_batches_tracked.dtype == torch.int64:
             nbt = bn.num_batches_tracked
+            # the kernel increments the counter (and moves the running statistics) through raw pointers: bump the counter's version by
+            # hand, or the folded-BatchNorm caches keyed by it (conv2d_hip, gconv3x3_hip ...) would serve the statistics of BEFORE this
+            # step to the next eval() call
+            torch.autograd.graph.increment_version(nbt)
         elif bn.num_batches_tracked is not None:
             bn.num_batches_tracked += 1
     return track, momentum, nbt

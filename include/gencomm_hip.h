@@ -757,6 +757,36 @@ int gencomm_pyramid_score_fwd(const float* x, const float* weight, const float* 
                               int W, void* stream);
 int gencomm_warp_weightfuse_fwd(const float* x, const float* score, const double* theta, const int* scene_off, float* out, int B, int n, int C, int H,
                                 int W, void* stream);
+/* Training HEAL's PyramidFusion (csrc/pyramid_bwd_kernels.h; additive, ABI v12): the adjoints of the four entries above.  No float atomics,
+ * every output element is written once, every parameter gradient is a sum of per-workgroup partials (scratch) added in index order: two
+ * runs give the same bits.  Status 2 for a scratch smaller than the matching _scratch_floats query (-1 outside the domain).
+ *   gencomm_gconv3x3_prepare_t   weight -> packed_t[((g cpg + co) 9 + tap) cpg + ci] = weight[g cpg + co][ci][8 - tap]: the pack of the
+ *                              input gradient (channels swapped inside each group, taps flipped).
+ *   gencomm_gconv3x3_dgrad     dx [n][C][H][W] from dy [n][C][Ho][Wo] (H, W: the FORWARD INPUT's size, odd sizes included): the forward
+ *                              tiles on dy with packed_t; unit_scale / zero_shift: [C] ones / zeros.  Stride 2 spreads dy onto the
+ *                              stride-1 grid first, into `spread` (n C H W floats; may be NULL at stride 1).
+ *   gencomm_gconv3x3_wgrad_fixed  dw [C][cpg][3][3] = sum over maps and output pixels of dy (x) x; no bias.
+ *   gencomm_pyramid_score_bwd  with sg = sigmoid(occ): d_pre = d_occ + d_score mask sg (1 - sg); dx = d_pre weight[c], dw[c] = sum d_pre
+ *                              x[c], db = sum d_pre.  occ: the forward's output.  rect as in the forward (the module passes none in
+ *                              train() mode, as the reference skips the crop there).  d_occ or d_score may be NULL (not both); dx may be
+ *                              NULL; dw and db may be NULL together (a frozen head: no scratch is needed then).
+ *   gencomm_warp_weightfuse_bwd  from x, score, theta, scene_off (as given to the forward) and dout [B][C][H][W]: dx [n][C][H][W] and
+ *                              dscore [n][1][H][W].  The shares are recomputed with the forward's cells; dscore is exactly 0 where the
+ *                              warped score was 0 and where nobody scores; an agent outside the map gets zeros; an agent under the exact
+ *                              identity gets dx = p dout without interpolation.  Gathered per source pixel for every transform (a
+ *                              singular one scans the map). */
+int gencomm_gconv3x3_prepare_t(const float* weight, float* packed_t, int cpg, void* stream);
+int gencomm_gconv3x3_dgrad(const float* dy, const float* packed_t, const float* unit_scale, const float* zero_shift, float* dx, float* spread, int n,
+                           int C, int cpg, int H, int W, int stride, void* stream);
+long long gencomm_gconv3x3_wgrad_fixed_scratch_floats(int n, int cpg, int H, int W, int stride);
+int gencomm_gconv3x3_wgrad_fixed(const float* x, const float* dy, float* dw, int n, int C, int cpg, int H, int W, int stride, float* scratch,
+                                 long long scratch_floats, void* stream);
+long long gencomm_pyramid_score_bwd_scratch_floats(int n, int C, int H, int W);
+int gencomm_pyramid_score_bwd(const float* x, const float* weight, const float* occ, const int* rect, const float* d_occ, const float* d_score,
+                              float* dx, float* dw, float* db, int n, int C, int H, int W, float* scratch, long long scratch_floats, void* stream);
+long long gencomm_warp_weightfuse_bwd_scratch_floats(int n, int H, int W);
+int gencomm_warp_weightfuse_bwd(const float* x, const float* score, const double* theta, const int* scene_off, const float* dout, float* dx,
+                                float* dscore, float* scratch, long long scratch_floats, int B, int n, int C, int H, int W, void* stream);
 /* MPDA's feature aligner (opencood/models/mpda_modules/wg_fusion_modules.py, resizer.py; csrc/mpda_kernels.h; additive, ABI v12).  fp32 NCHW
  * in, out and accumulation; every output element is stored exactly once, no atomics: two runs give the same bits.
  *   gencomm_quad_attn_fwd      attention inside 2 x 2 groups, by index arithmetic on the maps (nothing is rearranged in memory).  With
