@@ -14,6 +14,11 @@
 
 namespace gc {
 
+// The cross-unit contract: this header is compiled with contraction on (`fast`, the build's default), stated here so that it does not
+// follow from what an includer happened to parse before it.  Every warp kernel in both translation units inherits its rounding from
+// this one place, and that is what makes recomputed winners and re-derived cells agree with the forward.
+#pragma clang fp contract(fast)
+
 // affine_grid base coordinate of index i on an axis of `size`, align_corners=False: (2i+1)/size - 1, in float64 like theta
 __device__ __forceinline__ double fuse_base(int i, int size) { return (2.0 * i + 1.0) / (double)size - 1.0; }
 

@@ -8,12 +8,12 @@
 #include "fusion_kernels.h"
 #include "msgext_host.h"
 #include "noise_kernels.h"
-#include "pillar_kernels.h"
 #include "pfn_kernels.h"
+#include "pillar_kernels.h"
 #include "train_kernels.h"
-#include "wgrad_h3_kernels.h"
 #include "unet_bwd_host.h"
 #include "unet_host.h"
+#include "wgrad_h3_kernels.h"
 
 #include <algorithm>
 #include <atomic>

@@ -10,25 +10,23 @@
 #include "common.h"
 #include "codebook_bwd_kernels.h"
 #include "codebook_kernels.h"
-#include "convnext_kernels.h"
 #include "convnext_bwd_kernels.h"
+#include "convnext_kernels.h"
 #include "iou3d_kernels.h"
 #include "loss_kernels.h"
 #include "lss_kernels.h"
+#include "mpda_bwd_kernels.h"
+#include "mpda_kernels.h"
+#include "pyramid_bwd_kernels.h"
+#include "pyramid_kernels.h"
 #include "sparse_kernels.h"
 #include "swap_attn_bwd_kernels.h"
 #include "swap_attn_kernels.h"
 #include "target_kernels.h"
 #include "v2v_kernels.h"
 #include "v2xvit_kernels.h"
-#include "pyramid_kernels.h"   // out of alphabetical order on purpose: fuse_cell.h must first be parsed where v2v_kernels.h includes it (the
-                               // headers between iou3d_kernels.h and swap_attn_bwd_kernels.h run under `fp contract(off)`), or the warp kernels of
-                               // this unit stop matching the fusion kernels of gencomm_abi.hip bit for bit
-#include "pyramid_bwd_kernels.h"   // directly behind pyramid_kernels.h: the same contract state, so the recomputed shares are the forward's
 #include "voxel_batch_kernels.h"
 #include "voxel_kernels.h"
-#include "mpda_kernels.h"      // last: it sets `fp contract(off)` for itself and leaves `fast`, the state the headers above end in
-#include "mpda_bwd_kernels.h"  // after mpda_kernels.h (QuadTokens, resize_source); the same contract discipline
 
 using namespace gc;
 

@@ -169,4 +169,6 @@ __global__ __launch_bounds__(64) void iou3d_nms_reduce_kernel(int n, const unsig
   if (lane == 0) *count = num;
 }
 
+#pragma clang fp contract(fast)   // the build's default: no header leaves contraction off for whatever is included next
+
 }  // namespace gc

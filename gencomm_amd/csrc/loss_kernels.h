@@ -13,6 +13,12 @@
 
 namespace gc {
 
+// Contraction is off in this header for a historical reason, not a numerical one: since it was written it has been compiled behind
+// iou3d_kernels.h, which used to leave `off` in force for every later include of its translation unit.  Its float64 comparisons and
+// golden fixtures were taken on these bits, so the mode is pinned here rather than inherited; nothing in the arithmetic below is
+// known to need it.
+#pragma clang fp contract(off)
+
 constexpr int kLossMaxAnchors = 8;
 
 struct HeadLossArgs {
@@ -341,5 +347,7 @@ __global__ __launch_bounds__(256) void depth_focal_loss_kernel(const DepthFocalA
   __syncthreads();
   if (tid == 0) atomicAdd(a.sum, (s_red[0] + s_red[1] + s_red[2] + s_red[3]) * (double)a.scale);
 }
+
+#pragma clang fp contract(fast)
 
 }  // namespace gc

@@ -31,6 +31,12 @@
 
 namespace gc {
 
+// Contraction is off in this header for a historical reason, not a numerical one: since it was written it has been compiled behind
+// iou3d_kernels.h, which used to leave `off` in force for every later include of its translation unit.  Its float64 comparisons and
+// golden fixtures were taken on these bits, so the mode is pinned here rather than inherited; nothing in the arithmetic below is
+// known to need it.
+#pragma clang fp contract(off)
+
 struct LssGeom {
   float lo[3], dx[3];   // bx - dx / 2 and dx (float32, as the reference's tensors)
   int nx, ny, nz;       // cells per axis
@@ -499,5 +505,7 @@ __global__ __launch_bounds__(256) void stem7x7_wgrad_reduce_kernel(const float* 
   dw[i] = s;
 }
 inline int stem7x7_split(long long P) { return (int)std::min<long long>(kStemMaxSplit, (P + kStemPx - 1) / kStemPx); }
+
+#pragma clang fp contract(fast)
 
 }  // namespace gc

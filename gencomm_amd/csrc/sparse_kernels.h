@@ -23,6 +23,12 @@
 
 namespace gc {
 
+// Contraction is off in this header for a historical reason, not a numerical one: since it was written it has been compiled behind
+// iou3d_kernels.h, which used to leave `off` in force for every later include of its translation unit.  Its float64 comparisons and
+// golden fixtures were taken on these bits, so the mode is pinned here rather than inherited; nothing in the arithmetic below is
+// known to need it.
+#pragma clang fp contract(off)
+
 constexpr long long kSpNoKey = 0x7FFFFFFFFFFFFFFFLL;
 using f32x16s = __attribute__((ext_vector_type(16))) float;
 
@@ -640,5 +646,7 @@ __global__ __launch_bounds__(256) void sp_wgrad_kernel(const SpWgradArgs a) {
     if (acc[e] != 0.f) atomicAdd(&a.dw[((size_t)co * a.K + o) * Cin + ci], acc[e]);
   }
 }
+
+#pragma clang fp contract(fast)
 
 }  // namespace gc

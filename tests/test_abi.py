@@ -215,3 +215,53 @@ def test_code_object_keeps_mixed_type_matrix_instructions_apart(tmp_path):
     # the detector itself: the pair hipcc produced before the order was pinned
     sample = "\n0000 <k>:\n\tv_mfma_f32_16x16x32_bf8_bf8 v[18:21], v[22:23], v[18:19], v[2:5]\n\tv_mfma_f32_16x16x32_f16 v[18:21], v[36:39], v[58:61], v[18:21]\n"
     assert len(_mfma_hazard_violations(sample)) == 1
+
+
+def _contract_violations(text):
+    """File-scope `#pragma clang fp contract(...)` stays in force across #include boundaries until the next one, and the target has no
+    push / pop: so every file-scope `off` must be answered by `fast` (the build's default) in the same file, with no #include in
+    between. A file may open by stating `fast`. Pragmas inside a function body end with their block and are not looked at; namespace and
+    extern "C" braces count as file scope. Returns what breaks the rule."""
+    bad, state, seen, scopes = [], "fast", 0, []   # scopes: one entry per open brace, True for a namespace / linkage brace
+    for no, line in enumerate(re.sub(r"/\*.*?\*/", lambda m: "\n" * m.group(0).count("\n"), text, flags=re.S).split("\n"), 1):
+        if re.match(r"\s*#\s*include\b", line):
+            if state == "off":
+                bad.append(f"line {no}: #include while contraction is off")
+            continue
+        line = re.sub(r"//.*", "", re.sub(r'"(\\.|[^"\\])*"|\'(\\.|[^\'\\])\'', "", line))
+        m = re.match(r"\s*#\s*pragma\s+clang\s+fp\s+contract\s*\((\w+)\)", line)
+        if m and not any(not ns for ns in scopes):
+            mode, seen = m.group(1), seen + 1
+            if mode not in ("off", "fast") or (mode == state and not (mode == "fast" and seen == 1)):
+                bad.append(f"line {no}: contract({mode}) while contraction is {state}")
+            state = mode
+        for i, ch in enumerate(line):
+            if ch == "{":
+                scopes.append(re.search(r"(namespace(\s+\w+)?|extern)\s*$", line[:i]) is not None)
+            elif ch == "}" and scopes:
+                scopes.pop()
+    if state != "fast":
+        bad.append("contraction is still off at the end of the file")
+    return bad
+
+
+def test_fp_contraction_is_a_property_of_each_file():
+    """No file under csrc/ hands a contraction mode other than the build's default to whatever is parsed after it, so no kernel's
+    rounding depends on the order of the #include lines -- which both translation units therefore keep sorted."""
+    from gencomm_amd import _lib
+    files = sorted(os.listdir(_lib.CSRC_DIR))
+    assert len(files) >= 50
+    for f in files:
+        assert _contract_violations(open(os.path.join(_lib.CSRC_DIR, f)).read()) == [], f
+    for src in _lib.hip_sources():
+        own = re.findall(r'^#include "(\w+\.h)"', open(src).read(), flags=re.M)   # not ../../include/gencomm_hip.h
+        assert own[0] == "common.h" and own[1:] == sorted(own[1:]) and len(own) >= 10, (src, own)
+    # the detector itself: a header that turns contraction off and never back on, as iou3d_kernels.h once did ...
+    kernel = "__device__ float f(float a, float b) {\n  return a * b + a;   // { \"}\"\n}\n"
+    assert _contract_violations("#pragma once\nnamespace gc {\n#pragma clang fp contract(off)\n" + kernel + "}  // namespace gc\n")
+    assert not _contract_violations("#pragma once\nnamespace gc {\n#pragma clang fp contract(off)\n" + kernel + "#pragma clang fp contract(fast)\n}\n")
+    # ... an #include inside the region, a region opened twice ...
+    assert _contract_violations('#pragma clang fp contract(off)\n#include "common.h"\n#pragma clang fp contract(fast)\n')
+    assert _contract_violations("#pragma clang fp contract(off)\n#pragma clang fp contract(off)\n#pragma clang fp contract(fast)\n")
+    # ... and a pragma scoped to a function body, which is none of its business
+    assert not _contract_violations("namespace gc {\n__device__ float f(float a, float b) {\n#pragma clang fp contract(off)\n  return a * b + a;\n}\n}\n")
