@@ -20,9 +20,12 @@ Public surface mirrors the reference's plugin API:
     weighted_fuse(x, score, ...)       opencood/models/fuse_modules/pyramid_fuse.py:17
     MPDAAlign(args)                    opencood/models/heter_model_baseline_w_mpda.py:232-262 (MPDA's feature aligner; a component; trainable=True: training on mpda_bwd.py), with
     LearnableResizer, SwapFusionEncoder, CrossDomainFusionEncoder, DAImgHead   opencood/models/mpda_modules/
+    PointPillarPyramidLoss(args)       opencood/loss/point_pillar_pyramid_loss.py:12 (HEAL's criterion; a component, in baseline_criteria.py)
+    PointPillarMPDALoss(args)          opencood/loss/point_pillar_mpda_loss.py:16 (MPDA's criterion; a component, in baseline_criteria.py)
 
 All compute runs in hand-written HIP kernels behind the C ABI of ``include/gencomm_hip.h``.
 """
+from .baseline_criteria import PointPillarMPDALoss, PointPillarPyramidLoss
 from .cobevt import CoBEVT
 from .codebook import UMGMQuantizer
 from .cond_diff import GenComm
@@ -51,5 +54,5 @@ def set_denoise_dtype(dtype) -> None:
     _lib.check(_lib.lib().gencomm_set_mode(_lib.MODE_ARITH, value), "gencomm_set_mode")
 
 
-__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "MaxFusion", "Who2comFusion", "CoBEVT", "V2VNetFusion", "UMGMQuantizer", "Adapter", "Reverter", "PyramidFusion", "weighted_fuse", "MPDAAlign", "LearnableResizer", "SwapFusionEncoder", "CrossDomainFusionEncoder", "DAImgHead", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "regroup", "normalize_pairwise_tfm",
+__all__ = ["GenComm", "DiffusionUNet", "Enhancer", "AttFusion", "MaxFusion", "Who2comFusion", "CoBEVT", "V2VNetFusion", "UMGMQuantizer", "Adapter", "Reverter", "PyramidFusion", "weighted_fuse", "MPDAAlign", "LearnableResizer", "SwapFusionEncoder", "CrossDomainFusionEncoder", "DAImgHead", "MessageExtractorv2", "LiftSplatShoot", "PointPillarDepthLoss", "PointPillarPyramidLoss", "PointPillarMPDALoss", "regroup", "normalize_pairwise_tfm",
            "set_denoise_dtype"]

@@ -219,6 +219,8 @@ _SIGNATURES = {
     "gencomm_stem7x7_wgrad_scratch_floats": (_ll, [_i] * 5),
     "gencomm_stem7x7_wgrad": (_i, [_p, _p, _p] + [_i] * 5 + [_p, _ll, _p]),
     "gencomm_depth_focal_loss": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, _p]),
+    "gencomm_pyramid_occ_loss": (_i, [_p] * 6 + [_i] * 5 + [C.c_float] * 3 + [_p, _p]),
+    "gencomm_domain_bce_loss": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

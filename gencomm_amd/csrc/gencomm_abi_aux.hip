@@ -12,6 +12,7 @@
 #include "codebook_kernels.h"
 #include "convnext_bwd_kernels.h"
 #include "convnext_kernels.h"
+#include "criteria_kernels.h"
 #include "iou3d_kernels.h"
 #include "loss_kernels.h"
 #include "lss_kernels.h"
@@ -691,6 +692,44 @@ int gencomm_head_loss_mc(const float* cls, const float* reg, const void* labels,
   }
   HeadLossMcArgs<float> a{cls, reg, (const float*)labels, (const float*)targets, count, gcls, greg, sums, B, S, K, H * W, cls_weight, reg_weight};
   return head_loss_mc_enqueue(a, count, st);
+}
+
+// ---- the terms the HEAL and MPDA criteria add to the head loss (criteria_kernels.h)
+int gencomm_pyramid_occ_loss(const float* pos, const float* neg, const float* const* occ, float* const* grad, const int* relative_downsample,
+                             const float* weight, int levels, int B, int H, int W, int A, float pos_cls_weight, float gamma, float alpha,
+                             double* sums, void* stream) {
+  GC_CHECK_ARG(pos && neg && occ && grad && relative_downsample && weight && sums, "null pointer");
+  GC_CHECK_ARG(levels >= 1 && levels <= kOccMaxLevels, "1 <= levels <= 4");
+  GC_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && A >= 2 && (long long)H * W < (1LL << 24), "bad dims (A >= 2, H W < 2^24, B <= 65535)");
+  GC_CHECK_ARG(gamma >= 0.f, "gamma must not be negative");
+  OccLossArgs a{};
+  a.pos = pos; a.neg = neg; a.sums = sums; a.part = sums + 5;
+  a.B = B; a.H = H; a.W = W; a.A = A; a.levels = levels;
+  a.pos_cls_weight = pos_cls_weight; a.alpha = alpha; a.gamma = gamma; a.inv_bs = 1.0f / (float)B;
+  for (int i = 0; i < levels; ++i) {
+    const int k = relative_downsample[i];
+    GC_CHECK_ARG(k >= 1 && k <= H && k <= W, "relative_downsample must be in 1 .. min(H, W)");
+    GC_CHECK_ARG(occ[i] && grad[i], "null level pointer");
+    a.occ[i] = occ[i]; a.grad[i] = grad[i]; a.k[i] = k; a.Hl[i] = H / k; a.Wl[i] = W / k; a.weight[i] = weight[i];
+    a.cell_start[i + 1] = a.cell_start[i] + a.Hl[i] * a.Wl[i];
+  }
+  return occ_loss_enqueue(a, (hipStream_t)stream);
+}
+
+int gencomm_domain_bce_loss(const float* x, const int* source_index, int num_sources, float* grad, double* sums, int N, int C, int H, int W,
+                            void* stream) {
+  GC_CHECK_ARG(x && grad && sums && (source_index || num_sources == 0), "null pointer");
+  GC_CHECK_ARG(N >= 1 && N <= kBceMaxAgents && C >= 1 && H >= 1 && W >= 1 && (long long)C * H * W < (1LL << 30), "bad dims (N <= 1024, C H W < 2^30)");
+  GC_CHECK_ARG(num_sources >= 0 && num_sources <= N, "bad num_sources");
+  DomainBceArgs a{};
+  a.x = x; a.grad = grad; a.sums = sums; a.N = N; a.CHW = C * H * W;
+  a.blocks = std::min((a.CHW + 255) / 256, kBceBlocksPerAgent);
+  a.inv_numel = 1.0f / ((float)N * (float)a.CHW);
+  for (int i = 0; i < num_sources; ++i) {
+    GC_CHECK_ARG(source_index[i] >= 0 && source_index[i] < N, "source index outside [0, N)");
+    a.source[source_index[i] >> 6] |= 1ull << (source_index[i] & 63);
+  }
+  return domain_bce_enqueue(a, (hipStream_t)stream);
 }
 
 // ---- anchor target assignment (generate_label / generate_label_v2xreal) ---------------------------------------------

@@ -1083,6 +1083,28 @@ int gencomm_stem7x7_wgrad(const float* dy, const float* x, float* dw, int N, int
 int gencomm_depth_focal_loss(const float* depth_logit, const long long* target, float* grad, double* sum, int BN, int D, int H, int W,
                              float alpha, float gamma, float scale, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * The terms the HEAL and MPDA training criteria add to the detection-head loss (csrc/criteria_kernels.h). Value and gradient per call,
+ * two launches each, no atomics: two runs give the same bits, and nothing has to be zeroed by the caller.
+ *   gencomm_pyramid_occ_loss  calc_occ_loss of PointPillarPyramidLoss (point_pillar_pyramid_loss.py:69-103) over every pyramid level:
+ *                           pos / neg [B][H][W][A] float32 (A >= 2; anchors 0 and 1 are read), occ / grad: host arrays of `levels`
+ *                           (1..4) device pointers, level i [B][1][H / k_i][W / k_i] with k_i = relative_downsample[i] (host array;
+ *                           max_pool2d floors), weight: host array [levels]. Labels of a level cell: positive if any cell of its
+ *                           k x k window is positive on anchor 0 or 1, negative if every cell is negative on both; per (sample, level)
+ *                           norm = max(#positive, 1); sigmoid focal loss (gamma, alpha) with cell weight (pos * pos_cls_weight + neg) /
+ *                           norm; level loss = sum / B * weight[i]. sums: 5 + 8 B doubles (device): [0] total, [1..4] level losses
+ *                           (0 beyond `levels`), the rest scratch. grad_i = d total / d occ_i, every element written once.
+ *   gencomm_domain_bce_loss   the domain term of PointPillarMPDALoss (point_pillar_mpda_loss.py:124-150): x / grad [N][C][H][W]; target 1
+ *                           for the agents named in source_index (host array [num_sources], the first agent of every scene), 0
+ *                           elsewhere; sums: 1 + 32 N doubles (device): [0] mean over N C H W of max(x, 0) - x t + log1p(exp(-|x|)),
+ *                           the rest scratch; grad = (sigmoid(x) - t) / (N C H W). N <= 1024.
+ * -------------------------------------------------------------------------------------------- */
+int gencomm_pyramid_occ_loss(const float* pos, const float* neg, const float* const* occ, float* const* grad, const int* relative_downsample,
+                             const float* weight, int levels, int B, int H, int W, int A, float pos_cls_weight, float gamma, float alpha,
+                             double* sums, void* stream);
+int gencomm_domain_bce_loss(const float* x, const int* source_index, int num_sources, float* grad, double* sums, int N, int C, int H, int W,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
