@@ -283,17 +283,13 @@ __device__ __forceinline__ float gelu_grad_fast_f(float x) {
   return d;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Range guard of the fp16 hi/lo operand splits (conv8h_kernels.h).  A two-term split x = hi + lo needs |x| < 65504:
-//  * kernels whose operands are RAW tensors (conv_in's x_t / message channels, the Upsample conv's input, the unit-test
-//    entry) scale them by an exact power of two 2^-k chosen from a device-side bound on max|x| (act_scale: k = 0, i.e. no
-//    change at all, while the bound is below 2^14) and undo it in the epilogue -- the result is the fp32 one at any
-//    input magnitude a float can hold;
-//  * operands that are GroupNorm / LayerNorm outputs are bounded by |gamma| sqrt(group size) + |beta| whatever the
-//    input; every split kernel additionally runs with MODE.FP16_OVFL = 1, under which an overflowing f32 -> f16
-//    conversion saturates to +-65504 instead of producing inf: a pathological gamma degrades accuracy, it cannot
-//    create inf / NaN out of finite inputs.
-// ---------------------------------------------------------------------------------------------
+// The vector types of the fp16 operand splits (split_f16.h) and of the packed step noise below: declared once, here.
+typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+typedef float float2_t __attribute__((ext_vector_type(2)));
+typedef short short2_t __attribute__((ext_vector_type(2)));
+// Range guard of the fp16 hi/lo operand splits: see split_f16.h.  MODE.FP16_OVFL = 1 makes an overflowing f32 -> f16 conversion
+// saturate; act_scale is the power-of-two scale of kernels whose operands are raw tensors (1 while the bound is below 2^14).
 __device__ __forceinline__ void fp16_ovfl_clamp() { asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1"); }
 __device__ __forceinline__ float act_scale(float bound) {
   if (!(bound >= 16384.f)) return 1.0f;
@@ -504,12 +500,10 @@ __device__ __forceinline__ void bm_pair(float ur, uint32_t w, float k2, float& z
   asm("" : "+v"(zc), "+v"(zs));
 }
 // the pair as one packed fp16x2 dword (cosine branch in the low half)
-typedef _Float16 nz_half2_t __attribute__((ext_vector_type(2)));
-typedef float nz_float2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t bm_pair_h(float ur, uint32_t w, float k2) {
   float zc, zs;
   bm_pair(ur, w, k2, zc, zs);
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((nz_float2_t){zc, zs}, nz_half2_t));
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector((float2_t){zc, zs}, half2_t));
 }
 
 // 8 N(0,1) floats of one counter: z[2j], z[2j+1] = the pair of word j (q_sample's initial noise: element index / 8)
@@ -541,7 +535,7 @@ __device__ __forceinline__ void noise_pair_quad(uint64_t elem, uint32_t stream, 
   noise_pair_quad_h(elem, stream, seed, k2, h);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const nz_half2_t v = __builtin_bit_cast(nz_half2_t, h[j]);
+    const half2_t v = __builtin_bit_cast(half2_t, h[j]);
     z[j] = (float)v[0];
     z[4 + j] = (float)v[1];
   }

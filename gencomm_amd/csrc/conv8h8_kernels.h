@@ -9,6 +9,7 @@
 // (the Upsample convolution only exists at full resolution).
 #pragma once
 #include "conv8h_kernels.h"
+#include "split_f16.h"
 
 namespace gc {
 

@@ -6,20 +6,8 @@
 // v_fma) -- so conv8_kernel's 576 MFMAs and ~700 VALU instructions per tile-wave simply add up.  The f16/bf16
 // matrix pipe is separate (an MFMA holds the vector issue port for 8 of its 16 cycles) and 16x faster per MAC.
 //
-// Arithmetic (round 3: every operand carries all 24 bits of its fp32 value).  An activation x is split EXACTLY into three
-// terms x = hi + lo + t: hi = fp16(x), lo = fp16(x - hi), t = x - hi - lo (each difference is exact in fp32; t is 0 or
-// +-1 unit in the last place of x, i.e. a power of two, because two 11-bit terms and the sign of lo cover 23 of the 24
-// bits).  hi and lo live in fp16 planes of the LDS tile, t -- scaled by 2^20 -- in a bf8 (e5m2) plane, where a power of
-// two is exact.  A weight w (pre-scaled by a power of two so that the largest lies in [2^13, 2^14)) is split the same way
-// into three fp16 terms w1 + w2 + w3 (exact) and additionally rounded once to bf8, wb = bf8(w 2^-20).  A product block is
-// SIX matrix instructions into the same fp32 accumulators:
-//     hi w1 + lo w1 + hi w2 + lo w2 + hi w3        (five v_mfma_f32_16x16x32_f16: every fp16 x fp16 product exact)
-//   + t  wb                                        (one v_mfma_f32_16x16x32_bf8_bf8: the 2^-23-sized term to 3 bits)
-// The terms left out are lo w3, t w2, t w3 (<= 2^-33 |x w|) and the bf8 rounding of w in the last one
-// (2^-23 * 2^-3 = 2^-26 |x w|): a product is accurate to 2^-26 -- finer than the 2^-24 rounding of the fp32 accumulation
-// that the reference's own arithmetic has.  Round 2 used three instructions (hi w1 + lo w1 + hi w2) on two-term splits:
-// 2^-22 |x w| per product, "22-bit products".  Ranges: |x| < 65504 (range guard, common.h); t is carried for
-// |x| >= 2^-12 (below: absolute error <= 2^-36 per product), w3 for |w| >= 2^-14 max|w|.
+// Arithmetic: the exact three-term operand split of split_f16.h (x = hi + lo + t, w = w1 + w2 + w3 and a bf8 copy; SIX matrix
+// instructions per product block, products accurate to 2^-26); hi and lo live in fp16 planes of the LDS tile, t in a bf8 plane.
 // GENCOMM_MODE_ARITH = 1 selects the exact-fp32 conv8_kernel instead (unet_host.h).
 //
 // Mapping (one workgroup = 64x16 output pixels, 4 waves, wave w = rows 4w..4w+3):
@@ -33,14 +21,11 @@
 //   contiguous bytes (conflict-free) for every tap shift, and the staging pass (a thread holds a 4-pixel quad of all
 //   8 channels) writes one 16-B record per pixel, again 256 contiguous bytes per 16 lanes.
 #pragma once
+#include "split_f16.h"
 #include "unet_kernels.h"
 #include "unet_plan.h"
 
 namespace gc {
-
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef float float2_t __attribute__((ext_vector_type(2)));
 
 constexpr int HC_TW = 64, HC_TH = 16, HC_NT = 256, HC_LH = 18;
 constexpr int HC_SLOTS = 18;
@@ -54,55 +39,7 @@ constexpr int HC_WTAB3 = 3 * HC_WC3;         // 2688 dwords per 8-input-channel 
 static_assert(HC_WTAB3 == kWtab3, "unet_plan.h sizes the prepared blob with kWtab3");
 constexpr int HC_TPLANE = HC_PLANE / 2;      // 10368 bytes: the bf8 third-term plane (8-byte pixel records, same pixel order)
 constexpr int HC_TOFF = 2 * HC_PLANE;        // its byte offset in the tile
-constexpr float HC_TSCALE = 1048576.0f;      // 2^20: t is stored as bf8(t 2^20), the bf8 weight as bf8(w 2^-20)
 
-// exact two-term fp16 split of a pair of floats: hi = rne16(x), lo = rne16(x - hi)
-__device__ __forceinline__ void split_pair(float a, float b, uint32_t& hi, uint32_t& lo) {
-  const half2_t h = __builtin_convertvector((float2_t){a, b}, half2_t);
-  const float ra = a - (float)h[0], rb = b - (float)h[1];
-  const half2_t l = __builtin_convertvector((float2_t){ra, rb}, half2_t);
-  hi = __builtin_bit_cast(uint32_t, h);
-  lo = __builtin_bit_cast(uint32_t, l);
-}
-__device__ __forceinline__ void split_one(float a, uint16_t& hi, uint16_t& lo) {
-  const _Float16 h = (_Float16)a;
-  const _Float16 l = (_Float16)(a - (float)h);
-  hi = __builtin_bit_cast(uint16_t, h);
-  lo = __builtin_bit_cast(uint16_t, l);
-}
-
-// 1.0f the optimiser cannot see through: fma(x, one, -fp16) stays a fused multiply-add and is selected as ONE v_fma_mix_f32 (an fp16
-// operand read in place); written as x - (float)h it becomes v_cvt_f32_f16 + v_sub_f32.  One s_mov per kernel (the asm is pure: CSE'd).
-__device__ __forceinline__ float hc_one() {
-  float o;
-  asm("s_mov_b32 %0, 1.0" : "=s"(o));
-  return o;
-}
-// exact three-term split of a pair: hi / lo packed fp16 pairs, ta / tb = the third terms, UNSCALED: the 2^20 rides inside the
-// conversion to bf8 (bf8x2s / bf8x4s: v_cvt_scalef32_pk_bf8_f32 divides by its scale operand 2^-20 -- one multiply per element less)
-// 7 vector instructions per pair: 2 packed conversions + 4 v_fma_mix_f32 (+ the bf8 conversion at the caller).
-__device__ __forceinline__ void split3_pair(float a, float b, uint32_t& hi, uint32_t& lo, float& ta, float& tb) {
-  const float one = hc_one();
-  const half2_t h = __builtin_convertvector((float2_t){a, b}, half2_t);
-  const float ra = fmaf(a, one, -(float)h[0]), rb = fmaf(b, one, -(float)h[1]);
-  const half2_t l = __builtin_convertvector((float2_t){ra, rb}, half2_t);
-  ta = fmaf(ra, one, -(float)l[0]);
-  tb = fmaf(rb, one, -(float)l[1]);
-  hi = __builtin_bit_cast(uint32_t, h);
-  lo = __builtin_bit_cast(uint32_t, l);
-}
-// The same for PRODUCTS za ra, zb rb (the GroupNorm + SiLU staging below forms its activation as such a product): hi = fp16 of the
-// rounded product, first residual = fma(z, r, -hi) -- the exact product minus hi, rounded once -- and on from there as above.
-__device__ __forceinline__ void split3_prod_pair(float za, float ra, float zb, float rb, uint32_t& hi, uint32_t& lo, float& ta, float& tb) {
-  const float one = hc_one();
-  const half2_t h = __builtin_convertvector((float2_t){za * ra, zb * rb}, half2_t);
-  const float qa = fmaf(za, ra, -(float)h[0]), qb = fmaf(zb, rb, -(float)h[1]);
-  const half2_t l = __builtin_convertvector((float2_t){qa, qb}, half2_t);
-  ta = fmaf(qa, one, -(float)l[0]);
-  tb = fmaf(qb, one, -(float)l[1]);
-  hi = __builtin_bit_cast(uint32_t, h);
-  lo = __builtin_bit_cast(uint32_t, l);
-}
 // GroupNorm + SiLU in FIVE vector instructions per element (six before): the coefficients arrive pre-multiplied by -log2(e)
 // (hc_gn_coeff2: a2 = -log2e A, b2 = -log2e B), so z = a2 x + b2 = -log2e y with y = A x + B, e = 2^z = exp(-y),
 // d = -log2e (1 + e) as ONE fma, r = 1 / d, and SiLU(y) = y / (1 + e) = z r.  Out-of-image positions carry a2 = b2 = 0: z = 0 and
@@ -113,32 +50,6 @@ __device__ __forceinline__ void gn_silu_zr(float a2, float b2, float x, float& z
   z = fmaf(a2, x, b2);
   r = __builtin_amdgcn_rcpf(fmaf(cs, __builtin_amdgcn_exp2f(z), cs));
 }
-// two / four scaled third terms -> bf8 bytes (v_cvt_pk_bf8_f32: OCP e5m2, round to nearest even; powers of two are exact)
-__device__ __forceinline__ uint32_t bf8x2(float a, float b) {
-  return (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(a, b, 0, false) & 0xffffu;
-}
-__device__ __forceinline__ uint32_t bf8x4(float a, float b, float c, float d) {
-  int v = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, 0, false);
-  v = __builtin_amdgcn_cvt_pk_bf8_f32(c, d, v, true);
-  return (uint32_t)v;
-}
-
-// the same for UNSCALED third terms: bf8(t 2^20) through the scaled conversion of gfx950 (value / scale, scale = 2^-20; checked
-// bit for bit against multiply + convert on hardware)
-typedef short hc_s2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t bf8x2s(float a, float b) {
-  const hc_s2_t v = __builtin_amdgcn_cvt_scalef32_pk_bf8_f32((hc_s2_t){0, 0}, a, b, 1.0f / HC_TSCALE, false);
-  return (uint32_t)(uint16_t)v[0];
-}
-__device__ __forceinline__ uint32_t bf8x4s(float a, float b, float c, float d) {
-  // (an undefined "old" operand instead of the zero fill -- an empty volatile asm -- saves two v_mov per pixel and was measured 3.5 %
-  // SLOWER in latent_step_h_kernel, where the volatile statements pin the schedule: profiles/r5_conv8h_valu_diet.txt)
-  hc_s2_t u = {0, 0};
-  hc_s2_t v = __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(u, a, b, 1.0f / HC_TSCALE, false);
-  v = __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(v, c, d, 1.0f / HC_TSCALE, true);
-  return __builtin_bit_cast(uint32_t, v);
-}
-
 __device__ __forceinline__ int hc_addr(int row, int px /* -1 .. 64 */) {
   return row * HC_ROW + (px & 3) * HC_PHASE + ((px >> 2) + 1) * 16;
 }
@@ -991,23 +902,10 @@ __global__ __launch_bounds__(HC_NT, 3) void conv8hp_kernel(const Conv8Args a, in
 // Per tap group: fp16 terms w1, w2, w3 of w * scale ([term][lane][4 dwords], channels 2d, 2d+1 in dword d), then the
 // bf8 rounding of w * scale * 2^-20 ([lane][2 dwords], channel k in byte k).
 __global__ __launch_bounds__(256) void prep_conv8h_kernel(const float* __restrict__ w, float* __restrict__ dst, int IC) {
-  __shared__ float s_max[256];
   const int tid = threadIdx.x;
   float m = 0.f;
   for (int i = tid; i < 8 * IC * 9; i += 256) m = fmaxf(m, fabsf(w[i]));
-  s_max[tid] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) s_max[tid] = fmaxf(s_max[tid], s_max[tid + s]);
-    __syncthreads();
-  }
-  // power-of-two scale that puts the largest weight in [2^13, 2^14): the third terms of weights down to 2^-14 of the
-  // largest stay on fp16's 2^-24 grid (exact), the bf8 copies (x 2^-20) of weights down to 2^-7 of it stay normal;
-  // all-zero weights -> scale 1
-  const float wmax = s_max[0];
-  int ex = 0;
-  if (wmax > 0.f) (void)frexpf(wmax, &ex);  // wmax = f * 2^ex, f in [0.5, 1)
-  const float scale = wmax > 0.f ? ldexpf(1.0f, 14 - ex) : 1.0f;
+  const float scale = block_weight_scale(m);
   const int nsrc = IC / 8;
   uint32_t* __restrict__ out = reinterpret_cast<uint32_t*>(dst);
   auto weight = [&](int s, int c, int l, int ch) -> float {  // scaled weight of (source s, tap group c, lane l, channel ch)
@@ -1018,6 +916,8 @@ __global__ __launch_bounds__(256) void prep_conv8h_kernel(const float* __restric
   for (int i = tid; i < nsrc * HC_WTAB3; i += 256) {
     const int s = i / HC_WTAB3, rem = i - s * HC_WTAB3;
     const int c = rem / HC_WC3, q = rem - c * HC_WC3;
+    // wtab_pair / wtab_bf8 of split_f16.h written out: they take the eight weights of the lane, this kernel reads only the two or four the
+    // dword holds (handing all eight in changes its code: profiles/split_f16_refactor.md)
     if (q < 768) {
       const int d = q & 3, l = (q >> 2) & 63, term = q >> 8;
       uint16_t v[2];

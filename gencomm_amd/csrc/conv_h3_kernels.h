@@ -8,14 +8,12 @@
 // operand split exactly into fp16 hi + fp16 lo + a third term, products accurate to 2^-26: finer than the 2^-24 of an fp32 FMA chain) a
 // 16-channel x 9-tap chunk costs 54 x 32 = 1 728 matrix cycles instead of 72 x 64 x 2 = 9 216.
 //
-// Arithmetic.  Activations x (scaled by a running power of two xs so that the largest |x| seen so far lies in [2^13, 2^14): gradients are
-// scaled UP, large inputs down; when the exponent grows the accumulators are rescaled, exactly) = hi + lo + t with hi = fp16(x xs),
-// lo = fp16(x xs - hi), t = the rest (a power of two, stored as bf8(t 2^20)).  Weights (scaled PER OUTPUT ROW by the power of two that puts
-// the row's largest |w| into [2^13, 2^14): conv_prep_w3_kernel, undone in the epilogue) = w1 + w2 + w3 (fp16, exact) and wb = bf8(w 2^-20).
+// Arithmetic: the exact three-term split of split_f16.h.  Activations x carry its running power-of-two scale xs (RunScale: gradients are
+// scaled UP, large inputs down; when the exponent grows the accumulators are rescaled, exactly): x xs = hi + lo + t.  Weights are scaled PER
+// OUTPUT ROW by the power of two that puts the row's largest |w| into [2^13, 2^14) (conv_prep_w3_kernel, undone in the epilogue).
 //     acc  += w1 hi + w1 lo + w2 hi + w2 lo + w3 hi      (five v_mfma_f32_32x32x16_f16: every fp16 x fp16 product exact)
 //     accT += wb t                                       (one v_mfma_f32_32x32x16_bf8_bf8; its own accumulator: gfx950 forwards SrcC only
 //                                                         between matrix instructions of one input type)
-// Left out: lo w3, t w2, t w3 (<= 2^-33 |x w|) and the bf8 rounding of w in the last term (2^-26 |x w|).
 //
 // Mapping: GEMM rows = output channels (A operand = weights), columns = pixels (B operand), as conv2d_igemm_kernel: for a fixed
 // accumulator register the 32 lanes of a half-wave hold 32 consecutive pixels of one output channel (128-byte NCHW store runs).
@@ -29,7 +27,8 @@
 //     While stage s is on the matrix pipe, stage s + 1 (already in registers) is split and written to the other buffer and stage s + 2
 //     travels from memory; the workgroup-wide max |x| of a stage is published one barrier before it is needed: ONE barrier per stage.
 #pragma once
-#include "conv8h_kernels.h"   // split3_pair, bf8x4s, half8_t
+#include "conv8h_kernels.h"
+#include "split_f16.h"   // split3_pair, bf8x4s, RunScale, half8_t
 
 namespace gc {
 
@@ -86,11 +85,7 @@ __global__ __launch_bounds__(256) void conv_w3_rowscale_kernel(const PrepW3Args 
   mx = wave_max_nonneg(mx);
   if (l == 0) {
     float sc = 1.0f;
-    if (mx > 0.f && mx < 3.0e38f) {
-      int e;
-      (void)frexpf(mx, &e);                      // mx = f 2^e, f in [0.5, 1)
-      sc = ldexpf(1.0f, max(min(14 - e, 126), -126));
-    }
+    if (mx > 0.f && mx < 3.0e38f) sc = pow2_scale(mx, 126, -126);
     a.wsc[m] = 1.0f / sc;
   }
 }
@@ -112,16 +107,7 @@ __global__ __launch_bounds__(128) void conv_prep_w3_kernel(const PrepW3Args a) {
   }
   uint32_t p1[4], p2[4], p3[4], pb[2];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float x0 = v[2 * i], x1 = v[2 * i + 1];
-    const half2_t h1 = __builtin_convertvector((float2_t){x0, x1}, half2_t);
-    const float r0 = x0 - (float)h1[0], r1 = x1 - (float)h1[1];
-    const half2_t h2 = __builtin_convertvector((float2_t){r0, r1}, half2_t);
-    const half2_t h3 = __builtin_convertvector((float2_t){r0 - (float)h2[0], r1 - (float)h2[1]}, half2_t);
-    p1[i] = __builtin_bit_cast(uint32_t, h1);
-    p2[i] = __builtin_bit_cast(uint32_t, h2);
-    p3[i] = __builtin_bit_cast(uint32_t, h3);
-  }
+  for (int i = 0; i < 4; ++i) split3w_pair(v[2 * i], v[2 * i + 1], p1[i], p2[i], p3[i]);
   constexpr float TS = 1.0f / HC_TSCALE;
   pb[0] = bf8x4(v[0] * TS, v[1] * TS, v[2] * TS, v[3] * TS);
   pb[1] = bf8x4(v[4] * TS, v[5] * TS, v[6] * TS, v[7] * TS);
@@ -229,14 +215,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_h3_kernel(const Conv2dArgs a) {
     }
   };
   // the power of two that puts the largest |x| seen so far into [2^13, 2^14)
-  float run_max = 0.f;
-  auto scale_for = [&](int par, float prev) {
-    run_max = fmaxf(run_max, fmaxf(fmaxf(s_max[par][0], s_max[par][1]), fmaxf(s_max[par][2], s_max[par][3])));
-    if (!(run_max > 0.f)) return prev;
-    int e;
-    (void)frexpf(run_max, &e);
-    return ldexpf(1.0f, max(min(14 - e, 126), -126));
-  };
+  RunScale rs;
+  auto scale_for = [&](int par, float prev) { return rs.next(s_max[par], prev, 126, -126); };
 
   // ---- prologue: stage 0 into buffer 0, stage 1 in registers with its max published, stage 2 requested
   fetch(0, r1);
@@ -477,14 +457,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_h3l_kernel(const Conv2dArgs a, 
       }
     }
   };
-  float run_max = 0.f;
-  auto scale_for = [&](int par, float prev) {
-    run_max = fmaxf(run_max, fmaxf(fmaxf(s_max[par][0], s_max[par][1]), fmaxf(s_max[par][2], s_max[par][3])));
-    if (!(run_max > 0.f)) return prev;
-    int e;
-    (void)frexpf(run_max, &e);
-    return ldexpf(1.0f, max(min(14 - e, 126), -126));
-  };
+  RunScale rs;
+  auto scale_for = [&](int par, float prev) { return rs.next(s_max[par], prev, 126, -126); };
 
   // ---- prologue: sub-stage 0's weights and stage 0's activations in the LDS, stage 1's activations in registers with their max published
   dma_weights(0);

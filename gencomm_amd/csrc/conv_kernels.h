@@ -22,6 +22,7 @@
 // pixel-shuffle store for ConvTranspose2d with kernel == stride (a 1x1 conv to Cout*s*s channels).
 #pragma once
 #include "common.h"
+#include "split_f16.h"
 
 namespace gc {
 
@@ -225,7 +226,7 @@ __global__ void conv_prep_w_kernel(const PrepWArgs a) {
 
 // ---------------------------------------------------------------------------------------------
 // 1x1 stride-1 convolution (the Linear layers of the fusion transformers, message-extractor / head projections, the
-// training helpers) on the f16 matrix pipe with the exact hi/lo split arithmetic of conv8h_kernels.h / enhancer_kernels.h:
+// training helpers) on the f16 matrix pipe with the exact hi/lo split arithmetic of split_f16.h:
 // three v_mfma_f32_32x32x16_f16 per product block (hi*hi, hi*lo, lo*hi), fp32 accumulation, 22-bit products.
 //   out[co][p] = act(scale[co] * sum_ci W[co][ci] x[ci][p] + shift[co]) (+ res)
 // GEMM rows M = output channels (A = weights), columns N = pixels (B = x): for a fixed accumulator register the 32 lanes of a
@@ -239,23 +240,6 @@ __global__ void conv_prep_w_kernel(const PrepWArgs a) {
 // [2^13, 2^14) -- up for small inputs such as gradients, down for large ones -- and when it has to drop the accumulators are
 // rescaled (exact).  Any finite fp32 input gives finite, fp32-grade results relative to the tile's largest input.
 // ---------------------------------------------------------------------------------------------
-typedef _Float16 c1h8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 c1h2_t __attribute__((ext_vector_type(2)));
-typedef float c1f2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void c1_split8(const float (&v)[8], float mul, uint4& hi, uint4& lo) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a0 = v[2 * i] * mul, a1 = v[2 * i + 1] * mul;
-    const c1h2_t hh = __builtin_convertvector((c1f2_t){a0, a1}, c1h2_t);
-    const c1h2_t ll = __builtin_convertvector((c1f2_t){a0 - (float)hh[0], a1 - (float)hh[1]}, c1h2_t);
-    h[i] = __builtin_bit_cast(uint32_t, hh);
-    l[i] = __builtin_bit_cast(uint32_t, ll);
-  }
-  hi = make_uint4(h[0], h[1], h[2], h[3]);
-  lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
 template <int BN>  // pixels per workgroup: 64, or 32 when the launch would otherwise have too few workgroups to hide its load latency
 __global__ __launch_bounds__(256) void conv1x1_f16s_kernel(const Conv2dArgs a) {
   constexpr int BM = 128, KC = 32, RB = 80;  // row bytes: 32 halves + 8 pad (conflict-free ds_read_b128 phases)
@@ -294,7 +278,7 @@ __global__ __launch_bounds__(256) void conv1x1_f16s_kernel(const Conv2dArgs a) {
         aw[i][j] = (gm < a.CoutP && k < a.Cin) ? a.w[(size_t)k * a.CoutP + gm] : 0.f;
       }
   };
-  float xs = 1.0f, run_max = 0.f;  // running activation scale (power of two, workgroup-uniform) and the max|x| behind it
+  RunScale rs;  // running activation scale (power of two, workgroup-uniform) and the max|x| behind it
   fetch(0, vb, va);
   fetch(KC, wb, wa);  // all zeros beyond Cin
   int par = 0;
@@ -306,28 +290,25 @@ __global__ __launch_bounds__(256) void conv1x1_f16s_kernel(const Conv2dArgs a) {
     mx = wave_max_nonneg(mx);  // DPP ladder: no LDS round trips in the chunk loop's critical path
     if (l == 0) s_max[par][w] = mx;
     __syncthreads();  // also: every wave is done with the previous chunk in LDS
-    run_max = fmaxf(run_max, fmaxf(fmaxf(s_max[par][0], s_max[par][1]), fmaxf(s_max[par][2], s_max[par][3])));
-    if (run_max > 0.f) {  // scale = the power of two that puts the largest |x| seen so far into [2^13, 2^14) (fp16 max 65504; small
-      int e;              // inputs -- gradients -- are scaled UP so that their low parts stay normal fp16 numbers)
-      (void)frexpf(run_max, &e);  // run_max = f * 2^e, f in [0.5, 1)
-      const float ns = ldexpf(1.0f, min(14 - e, 100));
-      if (ns != xs) {     // the exponent grew (or this is the first non-zero chunk): rescale what is accumulated (exact)
-        const float ratio = ns / xs;
+    if (rs.fold(s_max[par]) > 0.f) {
+      const float ns = pow2_scale(rs.run_max, 100, INT_MIN);
+      if (ns != rs.xs) {  // the scale moves: rescale what is accumulated (RunScale, split_f16.h)
+        const float ratio = ns / rs.xs;
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc0[i] *= ratio; acc1[i] *= ratio; }
-        xs = ns;
+        rs.xs = ns;
       }
     }
     {
       uint4 hi, lo;
-      c1_split8(vb, xs, hi, lo);
+      split8(vb, rs.xs, hi, lo);
       if (bload) {
         *reinterpret_cast<uint4*>(Bh + bp * RB + 16 * bk) = hi;
         *reinterpret_cast<uint4*>(Bl + bp * RB + 16 * bk) = lo;
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        c1_split8(va[i], WS, hi, lo);
+        split8(va[i], WS, hi, lo);
         *reinterpret_cast<uint4*>(Ah + am * RB + 16 * (ak + 2 * i)) = hi;
         *reinterpret_cast<uint4*>(Al + am * RB + 16 * (ak + 2 * i)) = lo;
       }
@@ -340,25 +321,21 @@ __global__ __launch_bounds__(256) void conv1x1_f16s_kernel(const Conv2dArgs a) {
 #pragma unroll
     for (int ks = 0; ks < KC / 16; ++ks) {
       const int ko = 32 * ks + 16 * h;  // byte offset of this lane's 8 halves in the row
-      const c1h8_t ah = *reinterpret_cast<const c1h8_t*>(Ah + (32 * w + r) * RB + ko);
-      const c1h8_t al = *reinterpret_cast<const c1h8_t*>(Al + (32 * w + r) * RB + ko);
-      const c1h8_t b0h = *reinterpret_cast<const c1h8_t*>(Bh + r * RB + ko);
-      const c1h8_t b0l = *reinterpret_cast<const c1h8_t*>(Bl + r * RB + ko);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, b0h, acc0, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, b0l, acc0, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, b0h, acc0, 0, 0, 0);
+      const half8_t ah = *reinterpret_cast<const half8_t*>(Ah + (32 * w + r) * RB + ko);
+      const half8_t al = *reinterpret_cast<const half8_t*>(Al + (32 * w + r) * RB + ko);
+      const half8_t b0h = *reinterpret_cast<const half8_t*>(Bh + r * RB + ko);
+      const half8_t b0l = *reinterpret_cast<const half8_t*>(Bl + r * RB + ko);
+      mfma_split3(ah, al, b0h, b0l, acc0);
       if constexpr (BN == 64) {
-        const c1h8_t b1h = *reinterpret_cast<const c1h8_t*>(Bh + (32 + r) * RB + ko);
-        const c1h8_t b1l = *reinterpret_cast<const c1h8_t*>(Bl + (32 + r) * RB + ko);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, b1h, acc1, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, b1l, acc1, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, b1h, acc1, 0, 0, 0);
+        const half8_t b1h = *reinterpret_cast<const half8_t*>(Bh + (32 + r) * RB + ko);
+        const half8_t b1l = *reinterpret_cast<const half8_t*>(Bl + (32 + r) * RB + ko);
+        mfma_split3(ah, al, b1h, b1l, acc1);
       }
     }
   }
 
   // epilogue: register = GEMM row (output channel, or channel x sub-pixel of a ConvTranspose2d with kernel == stride), lane (r) = pixel column
-  const float unscale = 1.0f / (WS * xs);
+  const float unscale = 1.0f / (WS * rs.xs);
   const int ups = a.ups, s2 = ups * ups;
   const size_t oplane = (size_t)HW * s2;
   float* __restrict__ yn = a.y + ((size_t)n * a.out_ctotal + a.out_coff) * oplane;
@@ -457,7 +434,7 @@ __global__ __launch_bounds__(256) void conv3x3_f16s_kernel(const Conv2dArgs a) {
       for (int e = 0; e < 8; ++e) rw[j][e] = ok ? src[(size_t)e * 9 * a.CoutP] : 0.f;
     }
   };
-  float xs = 1.0f, run_max = 0.f;
+  RunScale rs;
   fetch(0);
   int par = 0;
   for (int c0 = 0; c0 < a.Cin; c0 += CC, par ^= 1) {
@@ -469,16 +446,13 @@ __global__ __launch_bounds__(256) void conv3x3_f16s_kernel(const Conv2dArgs a) {
     mx = wave_max_nonneg(mx);
     if (l == 0) s_max[par][wv] = mx;
     __syncthreads();  // also: every wave is done with the previous chunk in LDS
-    run_max = fmaxf(run_max, fmaxf(fmaxf(s_max[par][0], s_max[par][1]), fmaxf(s_max[par][2], s_max[par][3])));
-    if (run_max > 0.f) {
-      int e2;
-      (void)frexpf(run_max, &e2);
-      const float ns = ldexpf(1.0f, min(14 - e2, 100));
-      if (ns != xs) {
-        const float ratio = ns / xs;
+    if (rs.fold(s_max[par]) > 0.f) {
+      const float ns = pow2_scale(rs.run_max, 100, INT_MIN);
+      if (ns != rs.xs) {
+        const float ratio = ns / rs.xs;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] *= ratio;
-        xs = ns;
+        rs.xs = ns;
       }
     }
 #pragma unroll
@@ -486,7 +460,7 @@ __global__ __launch_bounds__(256) void conv3x3_f16s_kernel(const Conv2dArgs a) {
       const int it = tid + 256 * j, px = it >> 1, g = it & 1;
       if (it < NPI) {
         uint4 hi, lo;
-        c1_split8(rp[j], xs, hi, lo);
+        split8(rp[j], rs.xs, hi, lo);
         *reinterpret_cast<uint4*>(Ps + px * REC + 16 * g) = hi;
         *reinterpret_cast<uint4*>(Ps + px * REC + 32 + 16 * g) = lo;
       }
@@ -496,7 +470,7 @@ __global__ __launch_bounds__(256) void conv3x3_f16s_kernel(const Conv2dArgs a) {
       const int it = tid + 256 * j, co = it & 63, tg = it >> 6, tap = tg >> 1, g = tg & 1;
       if (it < NWI) {
         uint4 hi, lo;
-        c1_split8(rw[j], WS, hi, lo);
+        split8(rw[j], WS, hi, lo);
         *reinterpret_cast<uint4*>(Wsl + (tap * 64 + co) * REC + 16 * g) = hi;
         *reinterpret_cast<uint4*>(Wsl + (tap * 64 + co) * REC + 32 + 16 * g) = lo;
       }
@@ -508,18 +482,16 @@ __global__ __launch_bounds__(256) void conv3x3_f16s_kernel(const Conv2dArgs a) {
       const int ky = tap / 3, kx = tap - 3 * ky;
       const unsigned char* ap = Wsl + tap * 64 * REC + a_base;
       const unsigned char* bp = Ps + (ky * PW + kx) * REC + b_base;
-      const c1h8_t ah = *reinterpret_cast<const c1h8_t*>(ap), al = *reinterpret_cast<const c1h8_t*>(ap + 32);
-      const c1h8_t bh = *reinterpret_cast<const c1h8_t*>(bp), bl = *reinterpret_cast<const c1h8_t*>(bp + 32);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
+      const half8_t ah = *reinterpret_cast<const half8_t*>(ap), al = *reinterpret_cast<const half8_t*>(ap + 32);
+      const half8_t bh = *reinterpret_cast<const half8_t*>(bp), bl = *reinterpret_cast<const half8_t*>(bp + 32);
+      mfma_split3(ah, al, bh, bl, acc);
     }
   }
 
   // epilogue: lane = pixel (pyl, pxl), register = output channel row (as conv2d_igemm_kernel, ups == 1)
   const int oy = ty0 + pyl, ox = tx0 + pxl;
   if (oy >= a.Ho || ox >= a.Wo) return;
-  const float unscale = 1.0f / (WS * xs);
+  const float unscale = 1.0f / (WS * rs.xs);
   const size_t oplane = (size_t)a.Ho * a.Wo;
   float* __restrict__ yn = a.y + ((size_t)n * a.out_ctotal + a.out_coff) * oplane;
 #pragma unroll

@@ -8,6 +8,7 @@
 // f32-input matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulate).
 #pragma once
 #include "common.h"
+#include "split_f16.h"
 
 namespace gc {
 
@@ -313,10 +314,8 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(const GemmArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// The same GEMM on the f16 matrix pipe with EXACT THREE-TERM splits of both operands (the arithmetic of conv8h_kernels.h,
-// round 3): a token x = hi + lo + t (fp16, fp16, the last bit or two as a power of two -> bf8 after scaling by 2^20), a
-// weight w 2^12 = w1 + w2 + w3 (fp16) and its bf8 rounding wb = bf8(w 2^-8).  Per product block five
-// v_mfma_f32_32x32x16_f16 (hi w1, lo w1, hi w2, lo w2, hi w3) into the main accumulators and one
+// The same GEMM on the f16 matrix pipe with EXACT THREE-TERM splits of both operands (the arithmetic of split_f16.h; weights
+// scaled by 2^12).  Per product block five v_mfma_f32_32x32x16_f16 (hi w1, lo w1, hi w2, lo w2, hi w3) into the main accumulators and one
 // v_mfma_f32_32x32x16_bf8_bf8 (t wb) into accumulators OF ITS OWN, added in the epilogue: matrix instructions of different
 // input type never share registers (gfx950 does not forward SrcC between them; hipcc assumes it does --
 // tools/probes/mfma_mixed_dep_probe.hip).  Products to 2^-26; fp32 accumulation.  Tokens and weights are split while they are
@@ -326,40 +325,33 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(const GemmArgs a) {
 // Operand maps of v_mfma_f32_32x32x16_{f16, bf8_bf8}: A[i = lane & 31][k = 8 * (lane >> 5) .. +7], B[k same][j = lane & 31],
 // D as in the fp32 kernel.  K must be a multiple of 4 (it is C or 2C).
 // ---------------------------------------------------------------------------------------------
-typedef _Float16 eh8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 eh2_t __attribute__((ext_vector_type(2)));
-typedef float ef2_t __attribute__((ext_vector_type(2)));
-constexpr float ENH_TSCALE = 1048576.0f;  // 2^20: third terms are stored as bf8(t 2^20), bf8 weights as bf8(w scale 2^-20)
 constexpr float ENH_WS = 4096.0f;         // static weight scale of the Linear layers (2^12; |w| < 16 stays inside fp16)
-__device__ __forceinline__ uint32_t enh_bf8x4(float a, float b, float c, float d) {
-  int v = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, 0, false);
-  v = __builtin_amdgcn_cvt_pk_bf8_f32(c, d, v, true);
-  return (uint32_t)v;
-}
-// exact three-term split of four values: hi / lo as packed fp16, the third terms (x 2^20) as four bf8 bytes
+// exact three-term split of four values: hi / lo as packed fp16, the third terms (x 2^20) as four bf8 bytes.  The plain-subtraction form
+// of split_f16.h (split3_sub_pair), written out FOUR wide here: the two pairs' steps interleave, and issued pair after pair the staging
+// code of the GEMM, the partial convolution and the front kernel is scheduled differently (profiles/split_f16_refactor.md).
 __device__ __forceinline__ void enh_split4(float4 v, float mul, uint2& hi, uint2& lo, uint32_t& t8) {
   const float x[4] = {v.x * mul, v.y * mul, v.z * mul, v.w * mul};
-  const eh2_t h0 = __builtin_convertvector((ef2_t){x[0], x[1]}, eh2_t), h1 = __builtin_convertvector((ef2_t){x[2], x[3]}, eh2_t);
+  const half2_t h0 = __builtin_convertvector((float2_t){x[0], x[1]}, half2_t), h1 = __builtin_convertvector((float2_t){x[2], x[3]}, half2_t);
   const float r[4] = {x[0] - (float)h0[0], x[1] - (float)h0[1], x[2] - (float)h1[0], x[3] - (float)h1[1]};
-  const eh2_t l0 = __builtin_convertvector((ef2_t){r[0], r[1]}, eh2_t), l1 = __builtin_convertvector((ef2_t){r[2], r[3]}, eh2_t);
+  const half2_t l0 = __builtin_convertvector((float2_t){r[0], r[1]}, half2_t), l1 = __builtin_convertvector((float2_t){r[2], r[3]}, half2_t);
   hi = make_uint2(__builtin_bit_cast(uint32_t, h0), __builtin_bit_cast(uint32_t, h1));
   lo = make_uint2(__builtin_bit_cast(uint32_t, l0), __builtin_bit_cast(uint32_t, l1));
-  t8 = enh_bf8x4((r[0] - (float)l0[0]) * ENH_TSCALE, (r[1] - (float)l0[1]) * ENH_TSCALE, (r[2] - (float)l1[0]) * ENH_TSCALE,
-                 (r[3] - (float)l1[1]) * ENH_TSCALE);
+  t8 = bf8x4((r[0] - (float)l0[0]) * HC_TSCALE, (r[1] - (float)l0[1]) * HC_TSCALE, (r[2] - (float)l1[0]) * HC_TSCALE,
+             (r[3] - (float)l1[1]) * HC_TSCALE);
 }
-// a weight row segment: w1 / w2 / w3 as packed fp16 and the bf8 rounding of w scale 2^-20
+// a weight row segment: w1 / w2 / w3 as packed fp16 and the bf8 rounding of w scale 2^-20 (four wide for the same reason)
 __device__ __forceinline__ void enh_split4_w(float4 v, float mul, uint2& w1, uint2& w2, uint2& w3, uint32_t& wb) {
   const float x[4] = {v.x * mul, v.y * mul, v.z * mul, v.w * mul};
-  const eh2_t a0 = __builtin_convertvector((ef2_t){x[0], x[1]}, eh2_t), a1 = __builtin_convertvector((ef2_t){x[2], x[3]}, eh2_t);
+  const half2_t a0 = __builtin_convertvector((float2_t){x[0], x[1]}, half2_t), a1 = __builtin_convertvector((float2_t){x[2], x[3]}, half2_t);
   const float r[4] = {x[0] - (float)a0[0], x[1] - (float)a0[1], x[2] - (float)a1[0], x[3] - (float)a1[1]};
-  const eh2_t b0 = __builtin_convertvector((ef2_t){r[0], r[1]}, eh2_t), b1 = __builtin_convertvector((ef2_t){r[2], r[3]}, eh2_t);
-  const eh2_t c0 = __builtin_convertvector((ef2_t){r[0] - (float)b0[0], r[1] - (float)b0[1]}, eh2_t);
-  const eh2_t c1 = __builtin_convertvector((ef2_t){r[2] - (float)b1[0], r[3] - (float)b1[1]}, eh2_t);
+  const half2_t b0 = __builtin_convertvector((float2_t){r[0], r[1]}, half2_t), b1 = __builtin_convertvector((float2_t){r[2], r[3]}, half2_t);
+  const half2_t c0 = __builtin_convertvector((float2_t){r[0] - (float)b0[0], r[1] - (float)b0[1]}, half2_t);
+  const half2_t c1 = __builtin_convertvector((float2_t){r[2] - (float)b1[0], r[3] - (float)b1[1]}, half2_t);
   w1 = make_uint2(__builtin_bit_cast(uint32_t, a0), __builtin_bit_cast(uint32_t, a1));
   w2 = make_uint2(__builtin_bit_cast(uint32_t, b0), __builtin_bit_cast(uint32_t, b1));
   w3 = make_uint2(__builtin_bit_cast(uint32_t, c0), __builtin_bit_cast(uint32_t, c1));
-  const float k = 1.0f / ENH_TSCALE;
-  wb = enh_bf8x4(x[0] * k, x[1] * k, x[2] * k, x[3] * k);
+  const float k = 1.0f / HC_TSCALE;
+  wb = bf8x4(x[0] * k, x[1] * k, x[2] * k, x[3] * k);
 }
 
 template <int EPI>
@@ -424,17 +416,17 @@ __global__ __launch_bounds__(256) void gemm_f16s_mfma_kernel(const GemmArgs a) {
 #pragma unroll
     for (int ks = 0; ks < KC / 16; ++ks) {
       const int ko = 32 * ks + 16 * h;  // byte offset of this lane's 8 halves in the row (half of it in the bf8 planes)
-      const eh8_t ah = *reinterpret_cast<const eh8_t*>(Ah + (32 * w + r) * RB + ko);
-      const eh8_t al = *reinterpret_cast<const eh8_t*>(Al + (32 * w + r) * RB + ko);
+      const half8_t ah = *reinterpret_cast<const half8_t*>(Ah + (32 * w + r) * RB + ko);
+      const half8_t al = *reinterpret_cast<const half8_t*>(Al + (32 * w + r) * RB + ko);
       const long at = *reinterpret_cast<const long*>(At + (32 * w + r) * RT + (ko >> 1));
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         f32x16& acc = t == 0 ? acc0 : acc1;
         f32x16& act = t == 0 ? act0 : act1;
         const int row = 32 * t + r;
-        const eh8_t b1 = *reinterpret_cast<const eh8_t*>(B1 + row * RB + ko);
-        const eh8_t b2 = *reinterpret_cast<const eh8_t*>(B2 + row * RB + ko);
-        const eh8_t b3 = *reinterpret_cast<const eh8_t*>(B3 + row * RB + ko);
+        const half8_t b1 = *reinterpret_cast<const half8_t*>(B1 + row * RB + ko);
+        const half8_t b2 = *reinterpret_cast<const half8_t*>(B2 + row * RB + ko);
+        const half8_t b3 = *reinterpret_cast<const half8_t*>(B3 + row * RB + ko);
         const long bb = *reinterpret_cast<const long*>(Bb + row * RT + (ko >> 1));
         act = __builtin_amdgcn_mfma_f32_32x32x16_bf8_bf8(at, bb, act, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, b3, acc, 0, 0, 0);
@@ -488,48 +480,23 @@ struct EnhPconvHArgs {
 
 __global__ __launch_bounds__(256) void enh_prep_pconv_h_kernel(const float* __restrict__ w /*[dc][dc][3][3]*/, float* __restrict__ tab,
                                                               int dc, int nslice) {
-  __shared__ float s_max[256];
   const int tid = threadIdx.x;
   float m = 0.f;
   for (int i = tid; i < dc * dc * 9; i += 256) m = fmaxf(m, fabsf(w[i]));
-  s_max[tid] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) s_max[tid] = fmaxf(s_max[tid], s_max[tid + s]);
-    __syncthreads();
-  }
-  const float wmax = s_max[0];
-  int ex = 0;
-  if (wmax > 0.f) (void)frexpf(wmax, &ex);
-  const float scale = wmax > 0.f ? ldexpf(1.0f, 14 - ex) : 1.0f;  // largest weight in [2^13, 2^14): conv8h_kernels.h
+  const float scale = block_weight_scale(m);
   const int nob = dc / 16, total = nob * nslice * 896;
   uint32_t* __restrict__ out = reinterpret_cast<uint32_t*>(tab);
   for (int i = blockIdx.x * 256 + tid; i < total; i += gridDim.x * 256) {   // every workgroup derives the same scale
     const int blk = i / 896, q = i - blk * 896, sl = blk % nslice, ob = blk / nslice;
-    const int l = q < 768 ? (q >> 2) & 63 : (q - 768) >> 1;
+    const int l = q < 768 ? (q >> 2) & 63 : (q - 768) >> 1;   // wtab_lane(q), written out: see enh_prep_front_kernel
     const int mrow = l & 15, kg = l >> 4, oc = 16 * ob + mrow;
     float wv[8];
     for (int e = 0; e < 8; ++e) {
       const int kidx = 32 * sl + 8 * kg + e, tap = kidx / dc, ic = kidx - tap * dc;
       wv[e] = tap < 9 ? w[((size_t)oc * dc + ic) * 9 + tap] * scale : 0.f;
     }
-    if (q < 768) {
-      const int d = q & 3, term = q >> 8;
-      uint16_t v[2];
-      for (int e = 0; e < 2; ++e) {
-        const float x = wv[2 * d + e];
-        const _Float16 w1 = (_Float16)x;
-        const float r1 = x - (float)w1;
-        const _Float16 w2 = (_Float16)r1;
-        const _Float16 w3 = (_Float16)(r1 - (float)w2);
-        v[e] = __builtin_bit_cast(uint16_t, term == 0 ? w1 : term == 1 ? w2 : w3);
-      }
-      out[i] = (uint32_t)v[0] | ((uint32_t)v[1] << 16);
-    } else {
-      const int d = (q - 768) & 1;
-      const float k = 1.0f / ENH_TSCALE;
-      out[i] = enh_bf8x4(wv[4 * d] * k, wv[4 * d + 1] * k, wv[4 * d + 2] * k, wv[4 * d + 3] * k);
-    }
+    if (q < 768) out[i] = wtab_pair(q, wv);
+    else out[i] = wtab_bf8(q, wv);
   }
   if (blockIdx.x == 0 && tid < 64) tab[total + tid] = (tid & 1) ? scale : 1.0f / scale;
 }
@@ -572,17 +539,17 @@ __global__ __launch_bounds__(256) void enh_pconv_h_kernel(const EnhPconvHArgs a)
       const int tap = min(kidx0 / dc, 8), ic0 = kidx0 - (kidx0 / dc) * dc;  // slices past tap 8 carry zero weights
       const int dy = tap / 3, dx = tap - 3 * dy;
       const float* __restrict__ tb = a.tab + (size_t)(ob * a.nslice + sl) * 896;
-      eh8_t wa[3];
+      half8_t wa[3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) wa[k] = __builtin_bit_cast(eh8_t, *reinterpret_cast<const uint4*>(tb + (k * 64 + lane) * 4));
+      for (int k = 0; k < 3; ++k) wa[k] = __builtin_bit_cast(half8_t, *reinterpret_cast<const uint4*>(tb + (k * 64 + lane) * 4));
       const long wb = *reinterpret_cast<const long*>(tb + 768 + lane * 2);
       const int base = ((4 * wave + dy) * LW + ln + dx) * PB + ic0 * 2;
-      eh8_t bh[NG], bl[NG];
+      half8_t bh[NG], bl[NG];
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
         const int ad = base + (TW == 32 ? ((g >> 1) * LW + 16 * (g & 1)) : g * LW) * PB;
-        bh[g] = *reinterpret_cast<const eh8_t*>(pch_smem + ad);
-        bl[g] = *reinterpret_cast<const eh8_t*>(pch_smem + plane + ad);
+        bh[g] = *reinterpret_cast<const half8_t*>(pch_smem + ad);
+        bl[g] = *reinterpret_cast<const half8_t*>(pch_smem + plane + ad);
         const long bt = *reinterpret_cast<const long*>(pch_smem + 2 * plane + (ad >> 1));
         act[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8(wb, bt, act[g], 0, 0, 0);
       }
@@ -646,20 +613,13 @@ struct EnhFrontArgs {
 // out = {s1, 1 / s1, s2, 1 / s2}; all-zero or non-finite maxima keep ENH_WS.  grid = 2 (one workgroup per tensor).
 __global__ __launch_bounds__(256) void enh_wscale_kernel(const float* __restrict__ w1, long long n1, const float* __restrict__ w2, long long n2,
                                                          float* __restrict__ out) {
-  __shared__ float s_max[256];
   const float* __restrict__ w = blockIdx.x == 0 ? w1 : w2;
   const long long cnt = blockIdx.x == 0 ? n1 : n2;
   float m = 0.f;
   for (long long i = threadIdx.x; i < cnt; i += 256) m = fmaxf(m, fabsf(w[i]));
-  s_max[threadIdx.x] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) s_max[threadIdx.x] = fmaxf(s_max[threadIdx.x], s_max[threadIdx.x + s]);
-    __syncthreads();
-  }
+  const float wmax = block_max256(m);
   if (threadIdx.x == 0) {
     float scale = ENH_WS;
-    const float wmax = s_max[0];
     if (wmax > 0.f && wmax < INFINITY) {
       int ex = 0;
       (void)frexpf(wmax, &ex);                       // wmax = f 2^ex, f in [0.5, 1)
@@ -677,28 +637,15 @@ __global__ __launch_bounds__(256) void enh_prep_front_kernel(const float* __rest
   uint32_t* __restrict__ out = reinterpret_cast<uint32_t*>(tab);
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
     const int blk = i / 896, qq = i - blk * 896, ks = blk % ksteps, q = blk / ksteps;
+    // (wtab_lane(qq) written out in the three Enhancer prep kernels: through the function the compiler proves one more zero bit of l and
+    // an address mask of these kernels changes: profiles/split_f16_refactor.md)
     const int l = qq < 768 ? (qq >> 2) & 63 : (qq - 768) >> 1;
     const int m = l & 31, kg = l >> 5;
     const int row = m < 16 ? 16 * q + m : hid + 16 * q + (m - 16);
     float wv[8];
     for (int e = 0; e < 8; ++e) wv[e] = w1[(size_t)row * C + 16 * ks + 8 * kg + e] * WS1;
-    if (qq < 768) {
-      const int d = qq & 3, term = qq >> 8;
-      uint16_t v[2];
-      for (int e = 0; e < 2; ++e) {
-        const float x = wv[2 * d + e];
-        const _Float16 a1 = (_Float16)x;
-        const float r1 = x - (float)a1;
-        const _Float16 a2 = (_Float16)r1;
-        const _Float16 a3 = (_Float16)(r1 - (float)a2);
-        v[e] = __builtin_bit_cast(uint16_t, term == 0 ? a1 : term == 1 ? a2 : a3);
-      }
-      out[i] = (uint32_t)v[0] | ((uint32_t)v[1] << 16);
-    } else {
-      const int d = (qq - 768) & 1;
-      const float k = 1.0f / ENH_TSCALE;
-      out[i] = enh_bf8x4(wv[4 * d] * k, wv[4 * d + 1] * k, wv[4 * d + 2] * k, wv[4 * d + 3] * k);
-    }
+    if (qq < 768) out[i] = wtab_pair(qq, wv);
+    else out[i] = wtab_bf8(qq, wv);
   }
 }
 
@@ -711,27 +658,12 @@ __global__ __launch_bounds__(256) void enh_prep_back_kernel(const float* __restr
   uint32_t* __restrict__ out = reinterpret_cast<uint32_t*>(tab);
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
     const int blk = i / 896, qq = i - blk * 896, ob = blk % nob, q = blk / nob;
-    const int l = qq < 768 ? (qq >> 2) & 63 : (qq - 768) >> 1;
+    const int l = qq < 768 ? (qq >> 2) & 63 : (qq - 768) >> 1;   // wtab_lane(qq), written out: see enh_prep_front_kernel
     const int oc = 32 * ob + (l & 31), kg = l >> 5;
     float wv[8];
     for (int e = 0; e < 8; ++e) wv[e] = w2[(size_t)oc * hid + 16 * q + 8 * kg + e] * WS2;
-    if (qq < 768) {
-      const int d = qq & 3, term = qq >> 8;
-      uint16_t v[2];
-      for (int e = 0; e < 2; ++e) {
-        const float x = wv[2 * d + e];
-        const _Float16 a1 = (_Float16)x;
-        const float r1 = x - (float)a1;
-        const _Float16 a2 = (_Float16)r1;
-        const _Float16 a3 = (_Float16)(r1 - (float)a2);
-        v[e] = __builtin_bit_cast(uint16_t, term == 0 ? a1 : term == 1 ? a2 : a3);
-      }
-      out[i] = (uint32_t)v[0] | ((uint32_t)v[1] << 16);
-    } else {
-      const int d = (qq - 768) & 1;
-      const float k = 1.0f / ENH_TSCALE;
-      out[i] = enh_bf8x4(wv[4 * d] * k, wv[4 * d + 1] * k, wv[4 * d + 2] * k, wv[4 * d + 3] * k);
-    }
+    if (qq < 768) out[i] = wtab_pair(qq, wv);
+    else out[i] = wtab_bf8(qq, wv);
   }
 }
 
@@ -789,14 +721,14 @@ __global__ __launch_bounds__(256, 3) void enh_front_h_kernel(const EnhFrontArgs 
   // matrix phase that consumed the previous set: they arrive during the GELU / depthwise phases.  The table (114 KB) does not
   // fit the 32 KB L1: fetched just before use, every k-step waited for an L2 round trip (2.07 ms per 16-agent launch; 32 waits
   // per workgroup).
-  eh8_t wa[C / 16][3];
+  half8_t wa[C / 16][3];
   long wbq[C / 16];
   auto load_chunk_operands = [&](int q) {
 #pragma unroll
     for (int ks = 0; ks < C / 16; ++ks) {
       const float* __restrict__ tb = a.tab + (size_t)(q * (C / 16) + ks) * 896;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) wa[ks][k] = __builtin_bit_cast(eh8_t, *reinterpret_cast<const uint4*>(tb + (k * 64 + lane) * 4));
+      for (int k = 0; k < 3; ++k) wa[ks][k] = __builtin_bit_cast(half8_t, *reinterpret_cast<const uint4*>(tb + (k * 64 + lane) * 4));
       wbq[ks] = *reinterpret_cast<const long*>(tb + 768 + lane * 2);
     }
   };
@@ -819,8 +751,8 @@ __global__ __launch_bounds__(256, 3) void enh_front_h_kernel(const EnhFrontArgs 
 #pragma unroll
     for (int ks = 0; ks < C / 16; ++ks) {
       const int ko = 32 * ks + 16 * h;
-      const eh8_t bh = *reinterpret_cast<const eh8_t*>(zh + pb * RB + ko);
-      const eh8_t bl = *reinterpret_cast<const eh8_t*>(zl + pb * RB + ko);
+      const half8_t bh = *reinterpret_cast<const half8_t*>(zh + pb * RB + ko);
+      const half8_t bl = *reinterpret_cast<const half8_t*>(zl + pb * RB + ko);
       const long bt = *reinterpret_cast<const long*>(zt + pb * RT + (ko >> 1));
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf8_bf8(wbq[ks], bt, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[ks][2], bh, acc, 0, 0, 0);
@@ -847,12 +779,12 @@ __global__ __launch_bounds__(256, 3) void enh_front_h_kernel(const EnhFrontArgs 
     }
     __syncthreads();
     // Linear2's operands of this chunk: requested now, they arrive during the depthwise phase
-    eh8_t w2a[3];
+    half8_t w2a[3];
     long w2b = 0;
     if (L2) {
       const float* __restrict__ tb = a.tab2 + (size_t)(q * 2 + (wave & 1)) * 896;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) w2a[k] = __builtin_bit_cast(eh8_t, *reinterpret_cast<const uint4*>(tb + (k * 64 + lane) * 4));
+      for (int k = 0; k < 3; ++k) w2a[k] = __builtin_bit_cast(half8_t, *reinterpret_cast<const uint4*>(tb + (k * 64 + lane) * 4));
       w2b = *reinterpret_cast<const long*>(tb + 768 + lane * 2);
     }
     {
@@ -878,8 +810,8 @@ __global__ __launch_bounds__(256, 3) void enh_front_h_kernel(const EnhFrontArgs 
       uint32_t t0, t1;
       enh_split4(*reinterpret_cast<const float4*>(gp), 1.0f, h0, l0, t0);
       enh_split4(*reinterpret_cast<const float4*>(gp + 4), 1.0f, h1, l1, t1);
-      const eh8_t ah = __builtin_bit_cast(eh8_t, make_uint4(h0.x, h0.y, h1.x, h1.y));
-      const eh8_t al = __builtin_bit_cast(eh8_t, make_uint4(l0.x, l0.y, l1.x, l1.y));
+      const half8_t ah = __builtin_bit_cast(half8_t, make_uint4(h0.x, h0.y, h1.x, h1.y));
+      const half8_t al = __builtin_bit_cast(half8_t, make_uint4(l0.x, l0.y, l1.x, l1.y));
       const long at = (long)(((unsigned long)t1 << 32) | (unsigned long)t0);
       __builtin_amdgcn_sched_barrier(0);
       acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf8_bf8(at, w2b, acc2, 0, 0, 0);

@@ -13,6 +13,7 @@
 #include "conv8b_kernels.h"
 #include "conv8h_kernels.h"
 #include "latent_kernels.h"
+#include "split_f16.h"
 
 namespace gc {
 
@@ -28,74 +29,44 @@ constexpr int HL_RING = (2 * (HC_TW + 4) + 2 * HL_LH5) * 8;  // floats: exact A'
 __global__ __launch_bounds__(256) void prep_latent_h_kernel(const float* __restrict__ wc5, const float* __restrict__ w_in /*[8][C+2][3][3]*/,
                                                            float* __restrict__ dst5, float* __restrict__ dstx,
                                                            float* __restrict__ dstc, int C) {
-  __shared__ float s_max[256];
   const int tid = threadIdx.x;
   const int CI = C + 2;
   float m = 0.f;
   for (int i = tid; i < 1600; i += 256) m = fmaxf(m, fabsf(wc5[i]));
   for (int i = tid; i < 8 * CI * 9; i += 256) m = fmaxf(m, fabsf(w_in[i]));  // message channels included (conv_in_h_kernel)
-  s_max[tid] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) s_max[tid] = fmaxf(s_max[tid], s_max[tid + s]);
-    __syncthreads();
-  }
-  const float wmax = s_max[0];
-  int ex = 0;
-  if (wmax > 0.f) (void)frexpf(wmax, &ex);
-  const float scale = wmax > 0.f ? ldexpf(1.0f, 14 - ex) : 1.0f;  // largest weight in [2^13, 2^14), see prep_conv8h_kernel
-  // entry q of a tap group's HC_WC3 dwords from the scaled weights of the eight channels of (group, lane)
-  auto entry = [&](int q, const float (&wv)[8]) -> uint32_t {
-    if (q < 768) {
-      const int d = q & 3, term = q >> 8;
-      uint16_t v[2];
-      for (int e = 0; e < 2; ++e) {
-        const float x = wv[2 * d + e];
-        const _Float16 w1 = (_Float16)x;
-        const float r1 = x - (float)w1;
-        const _Float16 w2 = (_Float16)r1;
-        const _Float16 w3 = (_Float16)(r1 - (float)w2);
-        v[e] = __builtin_bit_cast(uint16_t, term == 0 ? w1 : term == 1 ? w2 : w3);
-      }
-      return (uint32_t)v[0] | ((uint32_t)v[1] << 16);
-    }
-    const int d = (q - 768) & 1;
-    const float k = 1.0f / HC_TSCALE;
-    return bf8x4(wv[4 * d] * k, wv[4 * d + 1] * k, wv[4 * d + 2] * k, wv[4 * d + 3] * k);
-  };
-  auto lane_of = [](int q) { return q < 768 ? (q >> 2) & 63 : (q - 768) >> 1; };
+  const float scale = block_weight_scale(m);
   uint32_t* __restrict__ o5 = reinterpret_cast<uint32_t*>(dst5);
   for (int i = tid; i < HL_W5TAB3; i += 256) {
-    const int c = i / HC_WC3, q = i - c * HC_WC3, l = lane_of(q);
+    const int c = i / HC_WC3, q = i - c * HC_WC3, l = wtab_lane(q);
     const int mrow = l & 15, kg = l >> 4, r = mrow >> 3, oc = mrow & 7;
     const int t = 4 * c + kg, dyp = t / 5, dx = t - 5 * dyp, dy = dyp - r;
     const bool live = t < 30 && dy >= 0 && dy <= 4;
     float wv[8];
     for (int ch = 0; ch < 8; ++ch) wv[ch] = live ? wc5[(ch * 25 + dy * 5 + dx) * 8 + oc] * scale : 0.f;
-    o5[i] = entry(q, wv);
+    o5[i] = wtab_entry(q, wv);
   }
   if (tid < 64) dst5[HL_W5TAB3 + tid] = (tid & 1) ? scale : 1.0f / scale;
   uint32_t* __restrict__ ox = reinterpret_cast<uint32_t*>(dstx);
   for (int i = tid; i < (C / 8) * HC_WTAB3; i += 256) {
     const int s = i / HC_WTAB3, rem = i - s * HC_WTAB3;
-    const int c = rem / HC_WC3, q = rem - c * HC_WC3, l = lane_of(q);
+    const int c = rem / HC_WC3, q = rem - c * HC_WC3, l = wtab_lane(q);
     const int mrow = l & 15, kg = l >> 4, r = mrow >> 3, oc = mrow & 7;
     const int dyp = hc_tap_row(kg), dx = c, dy = dyp - r;
     const bool live = dy >= 0 && dy <= 2;
     float wv[8];
     for (int ch = 0; ch < 8; ++ch) wv[ch] = live ? w_in[(((size_t)oc * CI + 2 + s * 8 + ch) * 3 + dy) * 3 + dx] * scale : 0.f;
-    ox[i] = entry(q, wv);
+    ox[i] = wtab_entry(q, wv);
   }
   // the two message channels as an 8-channel chunk (channels 2..7 zero): chunk 0 of conv_in_h_kernel
   uint32_t* __restrict__ oc_ = reinterpret_cast<uint32_t*>(dstc);
   for (int i = tid; i < HC_WTAB3; i += 256) {
-    const int c = i / HC_WC3, q = i - c * HC_WC3, l = lane_of(q);
+    const int c = i / HC_WC3, q = i - c * HC_WC3, l = wtab_lane(q);
     const int mrow = l & 15, kg = l >> 4, r = mrow >> 3, oc = mrow & 7;
     const int dyp = hc_tap_row(kg), dx = c, dy = dyp - r;
     const bool live = dy >= 0 && dy <= 2;
     float wv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int ch = 0; ch < 2; ++ch) wv[ch] = live ? w_in[(((size_t)oc * CI + ch) * 3 + dy) * 3 + dx] * scale : 0.f;
-    oc_[i] = entry(q, wv);
+    oc_[i] = wtab_entry(q, wv);
   }
 }
 
@@ -301,46 +272,21 @@ __global__ __launch_bounds__(HC_NT, 3) void conv_in_h_kernel(const ConvInHArgs a
 // Needs W % 4 == 0.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void prep_conv_out_h_kernel(const float* __restrict__ w /*[C][8][3][3]*/, float* __restrict__ tab, int C) {
-  __shared__ float s_max[256];
   const int tid = threadIdx.x;
   float m = 0.f;
   for (int i = tid; i < C * 72; i += 256) m = fmaxf(m, fabsf(w[i]));
-  s_max[tid] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) s_max[tid] = fmaxf(s_max[tid], s_max[tid + s]);
-    __syncthreads();
-  }
-  const float wmax = s_max[0];
-  int ex = 0;
-  if (wmax > 0.f) (void)frexpf(wmax, &ex);
-  const float scale = wmax > 0.f ? ldexpf(1.0f, 14 - ex) : 1.0f;  // largest weight in [2^13, 2^14), see prep_conv8h_kernel
+  const float scale = block_weight_scale(m);
   const int nocb = (C + 15) / 16;
   uint32_t* __restrict__ out = reinterpret_cast<uint32_t*>(tab);
   for (int i = tid; i < nocb * HC_WTAB3; i += 256) {
     const int ob = i / HC_WTAB3, rem = i - ob * HC_WTAB3;
     const int c = rem / HC_WC3, q = rem - c * HC_WC3;
-    const int l = q < 768 ? (q >> 2) & 63 : (q - 768) >> 1;
+    const int l = wtab_lane(q);
     const int oc = 16 * ob + (l & 15), t = 4 * c + (l >> 4);
     float wv[8];
     for (int ch = 0; ch < 8; ++ch) wv[ch] = (t < 9 && oc < C) ? w[((size_t)oc * 8 + ch) * 9 + t] * scale : 0.f;
-    if (q < 768) {
-      const int d = q & 3, term = q >> 8;
-      uint16_t v[2];
-      for (int e = 0; e < 2; ++e) {
-        const float x = wv[2 * d + e];
-        const _Float16 w1 = (_Float16)x;
-        const float r1 = x - (float)w1;
-        const _Float16 w2 = (_Float16)r1;
-        const _Float16 w3 = (_Float16)(r1 - (float)w2);
-        v[e] = __builtin_bit_cast(uint16_t, term == 0 ? w1 : term == 1 ? w2 : w3);
-      }
-      out[i] = (uint32_t)v[0] | ((uint32_t)v[1] << 16);
-    } else {
-      const int d = (q - 768) & 1;
-      const float k = 1.0f / HC_TSCALE;
-      out[i] = bf8x4(wv[4 * d] * k, wv[4 * d + 1] * k, wv[4 * d + 2] * k, wv[4 * d + 3] * k);
-    }
+    if (q < 768) out[i] = wtab_pair(q, wv);
+    else out[i] = wtab_bf8(q, wv);
   }
   if (tid < 64) tab[nocb * HC_WTAB3 + tid] = (tid & 1) ? scale : 1.0f / scale;
 }

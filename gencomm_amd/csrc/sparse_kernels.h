@@ -20,6 +20,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "split_f16.h"
 
 namespace gc {
 
@@ -310,27 +311,19 @@ __global__ __launch_bounds__(256) void sp_conv_kernel(const SpConvArgs a) {
 }
 
 // The same gather-GEMM on the f16 matrix pipe (Cin = 32 or 64: the layers that take two thirds of the encoder's time) with the exact
-// hi/lo split of conv8h_kernels.h: per kernel offset CIN / 16 steps of v_mfma_f32_32x32x16_f16 x 3 split terms (12 MFMAs of 32 cycles
+// hi/lo split of split_f16.h: per kernel offset CIN / 16 steps of v_mfma_f32_32x32x16_f16 x 3 split terms (12 MFMAs of 32 cycles
 // at Cin = 64 against 32 of 64 cycles).  Gathered rows are channel-contiguous already, so a thread splits the 8 / 16 channels it
 // fetched and writes 16-byte record pieces; the prepared weights [offset][k pair][co][2] are read as 4 float2 per (co, k octet).
 // LDS records {CIN hi halves | CIN lo halves | 16 B pad} (an odd number of 16-byte units: conflict-free ds_read_b128 phases).
 // Activations carry the running power-of-two scale of conv1x1_f16s_kernel (workgroup max per offset; accumulators rescaled when the
 // exponent grows), weights are pre-multiplied by 2^6.
-typedef _Float16 sph8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 sph2_t __attribute__((ext_vector_type(2)));
-typedef float spf2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void sp_split8(const float (&v)[8], float mul, uint4& hi, uint4& lo) {  // exact two-term fp16 split of 8 scaled floats
-  uint32_t hh[4], ll[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a0 = v[2 * i] * mul, a1 = v[2 * i + 1] * mul;
-    const sph2_t x = __builtin_convertvector((spf2_t){a0, a1}, sph2_t);
-    const sph2_t y = __builtin_convertvector((spf2_t){a0 - (float)x[0], a1 - (float)x[1]}, sph2_t);
-    hh[i] = __builtin_bit_cast(uint32_t, x);
-    ll[i] = __builtin_bit_cast(uint32_t, y);
-  }
-  hi = make_uint4(hh[0], hh[1], hh[2], hh[3]);
-  lo = make_uint4(ll[0], ll[1], ll[2], ll[3]);
+// split8 of split_f16.h with the products formed HERE, under this header's contract(off): written inside split_f16.h (compiled `fast`)
+// the multiply fuses with the split's first subtraction and sp_conv_f16s_kernel<32> / <64> change.
+__device__ __forceinline__ void sp_scaled_split8(const float (&v)[8], float mul, uint4& hi, uint4& lo) {
+  split_pair(v[0] * mul, v[1] * mul, hi.x, lo.x);
+  split_pair(v[2] * mul, v[3] * mul, hi.y, lo.y);
+  split_pair(v[4] * mul, v[5] * mul, hi.z, lo.z);
+  split_pair(v[6] * mul, v[7] * mul, hi.w, lo.w);
 }
 template <int CIN>
 __global__ __launch_bounds__(256) void sp_conv_f16s_kernel(const SpConvArgs a) {
@@ -388,7 +381,7 @@ __global__ __launch_bounds__(256) void sp_conv_f16s_kernel(const SpConvArgs a) {
       }
     }
   };
-  float xs = 1.0f, run_max = 0.f;
+  RunScale rs;
   int par = 0;
   if (mask != 0u) {
     fetch(__builtin_ctz(mask));
@@ -399,24 +392,21 @@ __global__ __launch_bounds__(256) void sp_conv_f16s_kernel(const SpConvArgs a) {
       mx = wave_max_nonneg(mx);
       if (l == 0) s_max[par][wv] = mx;
       __syncthreads();   // every wave is done with the previous offset's tiles
-      run_max = fmaxf(run_max, fmaxf(fmaxf(s_max[par][0], s_max[par][1]), fmaxf(s_max[par][2], s_max[par][3])));
-      par ^= 1;
-      if (run_max > 0.f) {
-        int e2;
-        (void)frexpf(run_max, &e2);
-        const float ns = ldexpf(1.0f, min(14 - e2, 100));
-        if (ns != xs) {
-          const float ratio = ns / xs;
+      if (rs.fold(s_max[par]) > 0.f) {
+        const float ns = pow2_scale(rs.run_max, 100, INT_MIN);
+        if (ns != rs.xs) {
+          const float ratio = ns / rs.xs;
 #pragma unroll
           for (int i = 0; i < 16; ++i) acc[i] *= ratio;
-          xs = ns;
+          rs.xs = ns;
         }
       }
+      par ^= 1;
 #pragma unroll
       for (int e = 0; e < EPT; e += 8) {
         const float v8[8] = {va[e], va[e + 1], va[e + 2], va[e + 3], va[e + 4], va[e + 5], va[e + 6], va[e + 7]};
         uint4 hi, lo;
-        sp_split8(v8, xs, hi, lo);
+        sp_scaled_split8(v8, rs.xs, hi, lo);
         *reinterpret_cast<uint4*>(As + l * REC + (c0 + e) * 2) = hi;
         *reinterpret_cast<uint4*>(As + l * REC + LO + (c0 + e) * 2) = lo;
       }
@@ -424,7 +414,7 @@ __global__ __launch_bounds__(256) void sp_conv_f16s_kernel(const SpConvArgs a) {
       for (int j = 0; j < WIT; ++j) {
         const int it = tid + 256 * j, co = it & 63, g = it >> 6;
         uint4 hi, lo;
-        sp_split8(vb[j], WS, hi, lo);
+        sp_scaled_split8(vb[j], WS, hi, lo);
         *reinterpret_cast<uint4*>(Bs + co * REC + 16 * g) = hi;
         *reinterpret_cast<uint4*>(Bs + co * REC + LO + 16 * g) = lo;
       }
@@ -436,11 +426,9 @@ __global__ __launch_bounds__(256) void sp_conv_f16s_kernel(const SpConvArgs a) {
         for (int ks = 0; ks < CIN / 16; ++ks) {
           const unsigned char* ap = As + (sh * 32 + r) * REC + 32 * ks + 16 * h;
           const unsigned char* bp = Bs + (ch * 32 + r) * REC + 32 * ks + 16 * h;
-          const sph8_t ah = *reinterpret_cast<const sph8_t*>(ap), al = *reinterpret_cast<const sph8_t*>(ap + LO);
-          const sph8_t bh = *reinterpret_cast<const sph8_t*>(bp), bl = *reinterpret_cast<const sph8_t*>(bp + LO);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
+          const half8_t ah = *reinterpret_cast<const half8_t*>(ap), al = *reinterpret_cast<const half8_t*>(ap + LO);
+          const half8_t bh = *reinterpret_cast<const half8_t*>(bp), bl = *reinterpret_cast<const half8_t*>(bp + LO);
+          mfma_split3(ah, al, bh, bl, acc);
         }
       }
       if (mask == 0u) break;
@@ -449,7 +437,7 @@ __global__ __launch_bounds__(256) void sp_conv_f16s_kernel(const SpConvArgs a) {
   if (!co_live) return;
   const int co = co0 + ch * 32 + r;
   if (co >= a.Cout) return;
-  const float sc = a.scale[co] / (WS * xs), sf = a.shift[co];
+  const float sc = a.scale[co] / (WS * rs.xs), sf = a.shift[co];
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
     const int site = site0 + sh * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;

@@ -20,7 +20,8 @@
 // left margin); for kx = 0 / 2 they straddle it by one pixel -- the record, the dword left and the dword right of it are read ONCE per
 // (ky, step) and the two shifted operands are formed with v_alignbit (15 vector instructions per 18 matrix instructions).
 #pragma once
-#include "conv8h_kernels.h"   // split3_pair, half8_t, HC_TSCALE
+#include "conv8h_kernels.h"
+#include "split_f16.h"   // split3_pair, split3w_pair, half8_t, HC_TSCALE
 #include "train_kernels.h"
 
 namespace gc {
@@ -169,13 +170,7 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_h3_kernel(const Wgrad3x3Args 
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const float x0 = va[2 * i] * sA, x1 = va[2 * i + 1] * sA;
-        const half2_t h1 = __builtin_convertvector((float2_t){x0, x1}, half2_t);
-        const float r0 = x0 - (float)h1[0], r1 = x1 - (float)h1[1];
-        const half2_t h2 = __builtin_convertvector((float2_t){r0, r1}, half2_t);
-        const half2_t h3 = __builtin_convertvector((float2_t){r0 - (float)h2[0], r1 - (float)h2[1]}, half2_t);
-        p1[i] = __builtin_bit_cast(uint32_t, h1);
-        p2[i] = __builtin_bit_cast(uint32_t, h2);
-        p3[i] = __builtin_bit_cast(uint32_t, h3);
+        split3w_pair(x0, x1, p1[i], p2[i], p3[i]);
         p4[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector((float2_t){x0 * TS, x1 * TS}, half2_t));
       }
       unsigned char* pa = wg_smem + srow * L::SA + 32 * seg;

@@ -265,3 +265,40 @@ def test_fp_contraction_is_a_property_of_each_file():
     assert _contract_violations("#pragma clang fp contract(off)\n#pragma clang fp contract(off)\n#pragma clang fp contract(fast)\n")
     # ... and a pragma scoped to a function body, which is none of its business
     assert not _contract_violations("namespace gc {\n__device__ float f(float a, float b) {\n#pragma clang fp contract(off)\n  return a * b + a;\n}\n}\n")
+
+
+_SPLIT_HOME = {   # text of the exact fp16 split -> the only files under csrc/ that may hold it
+    r"typedef\s+_Float16\b[^;]*ext_vector_type": {"common.h"},              # the vector types (shared with the packed step noise)
+    r"__builtin_amdgcn_cvt_pk_bf8_f32": {"split_f16.h"},
+    r"__builtin_amdgcn_cvt_scalef32_pk_bf8_f32": {"split_f16.h"},
+}
+# the copies that went: sp_split8 too -- the sparse kernel forms its products under its own contraction and calls the shared split_pair
+_SPLIT_GONE = r"\b(c1_split8|sp_split8|enh_bf8x4|ENH_TSCALE|hc_s2_t|c1h[28]_t|c1f2_t|sph[28]_t|spf2_t|eh[28]_t|ef2_t|nz_half2_t|nz_float2_t)\b"
+
+
+def _split_strays(name, text):
+    """What a file says of the split arithmetic that only its home may say, or that nobody may say any more."""
+    bad = [pat for pat, home in _SPLIT_HOME.items() if name not in home and re.search(pat, text)]
+    return bad + sorted(set(m.group(0) for m in re.finditer(_SPLIT_GONE, text)))
+
+
+def test_the_fp16_split_has_one_home():
+    """The operand splits, the bf8 conversions and their vector types are written once (split_f16.h; the types in common.h) and included,
+    not copied under a new prefix by each layer that runs on this arithmetic."""
+    from gencomm_amd import _lib
+    files = sorted(os.listdir(_lib.CSRC_DIR))
+    assert "split_f16.h" in files and len(files) >= 50
+    text = {f: open(os.path.join(_lib.CSRC_DIR, f)).read() for f in files}
+    for f in files:
+        assert _split_strays(f, text[f]) == [], f
+    for pat, home in _SPLIT_HOME.items():   # ... and the home does hold it
+        assert all(re.search(pat, text[h]) for h in home), pat
+    users = [f for f in files if f != "split_f16.h" and re.search(r'^#include "split_f16\.h"', text[f], flags=re.M)]
+    assert len(users) >= 8 and re.search(r'^#include "common\.h"', text["split_f16.h"], flags=re.M), users
+    # the detector itself: a layer that declares the types again under its own prefix and converts to bf8 by hand ...
+    copy = "typedef _Float16 xh2_t __attribute__((ext_vector_type(2)));\nint v = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, 0, false);\n"
+    assert _split_strays("next_layer_kernels.h", copy) == list(_SPLIT_HOME)[:2]
+    assert _split_strays("split_f16.h", copy) == list(_SPLIT_HOME)[:1] and _split_strays("common.h", copy) == list(_SPLIT_HOME)[1:2]
+    # ... and one that calls the shared code, or names a retired copy
+    assert _split_strays("next_layer_kernels.h", "half2_t h; split8(v, xs, hi, lo); bf8x4(a, b, c, d);") == []
+    assert _split_strays("next_layer_kernels.h", "enh_bf8x4(a, b, c, d) * ENH_TSCALE; eh8_t x;") == ["ENH_TSCALE", "eh8_t", "enh_bf8x4"]
