@@ -66,6 +66,8 @@ _SIGNATURES = {
     "gencomm_enhancer_raw_floats": (_ll, [_i]),
     "gencomm_enhancer_workspace_bytes": (_ll, [_i, _i, _i, _i]),
     "gencomm_enhancer_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _ll, _p]),
+    "gencomm_enhancer_workspace_layout": (_i, [_i, _i, _i, _i, C.POINTER(_ll)]),
+    "gencomm_enhancer_fwd_stages": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _ll, _i, _i, _p]),
     "gencomm_msgext_num_params": (_i, [_i]),
     "gencomm_msgext_param_info": (_i, [_i, _i, C.c_char_p, _i, C.POINTER(_ll), C.POINTER(_ll)]),
     "gencomm_msgext_raw_floats": (_ll, [_i]),
@@ -387,6 +389,16 @@ def enhancer_param_table(Cch: int) -> List[Tuple[str, int, int]]:
         check(l.gencomm_enhancer_param_info(Cch, i, buf, 128, C.byref(numel), C.byref(off)), "gencomm_enhancer_param_info")
         out.append((buf.value.decode(), int(numel.value), int(off.value)))
     return out
+
+
+ENHANCER_WS_FIELDS = ("Y", "Z", "Zc", "Hd", "G", "O", "colsum", "gate")
+
+
+def enhancer_workspace_layout(n: int, Cch: int, H: int, W: int) -> dict:
+    """Byte offsets of the Enhancer's intermediates inside its workspace (gencomm_enhancer_workspace_layout), by name."""
+    off = (_ll * len(ENHANCER_WS_FIELDS))()
+    check(lib().gencomm_enhancer_workspace_layout(n, Cch, H, W, off), "gencomm_enhancer_workspace_layout")
+    return dict(zip(ENHANCER_WS_FIELDS, (int(v) for v in off)))
 
 
 def msgext_param_table(Cch: int) -> List[Tuple[str, int, int]]:

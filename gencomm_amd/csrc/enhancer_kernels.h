@@ -217,6 +217,7 @@ struct GemmArgs {
   const float* A; const float* Bw; const float* bias; const float* res;
   float* out; float* colsum;  // colsum [agents][N] (EPI 1)
   int M, N, K;                // per agent
+  const float* ws;            // f16-pipe kernel only: {power-of-two scale of Bw, 1 / it} (enh_wscale_kernel)
 };
 
 template <int EPI>
@@ -315,7 +316,8 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(const GemmArgs a) {
 
 // ---------------------------------------------------------------------------------------------
 // The same GEMM on the f16 matrix pipe with EXACT THREE-TERM splits of both operands (the arithmetic of split_f16.h; weights
-// scaled by 2^12).  Per product block five v_mfma_f32_32x32x16_f16 (hi w1, lo w1, hi w2, lo w2, hi w3) into the main accumulators and one
+// scaled by the tensor's power of two from enh_wscale_kernel: 2^12 while max |w| < 4).  Per product block five
+// v_mfma_f32_32x32x16_f16 (hi w1, lo w1, hi w2, lo w2, hi w3) into the main accumulators and one
 // v_mfma_f32_32x32x16_bf8_bf8 (t wb) into accumulators OF ITS OWN, added in the epilogue: matrix instructions of different
 // input type never share registers (gfx950 does not forward SrcC between them; hipcc assumes it does --
 // tools/probes/mfma_mixed_dep_probe.hip).  Products to 2^-26; fp32 accumulation.  Tokens and weights are split while they are
@@ -325,7 +327,8 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(const GemmArgs a) {
 // Operand maps of v_mfma_f32_32x32x16_{f16, bf8_bf8}: A[i = lane & 31][k = 8 * (lane >> 5) .. +7], B[k same][j = lane & 31],
 // D as in the fp32 kernel.  K must be a multiple of 4 (it is C or 2C).
 // ---------------------------------------------------------------------------------------------
-constexpr float ENH_WS = 4096.0f;         // static weight scale of the Linear layers (2^12; |w| < 16 stays inside fp16)
+constexpr float ENH_WS = 4096.0f;         // weight scale of the Linear layers for ordinary weights (2^12); enh_wscale_kernel lowers it per tensor
+                                          // once max |w| >= 4, so that no scaled weight reaches the end of fp16
 // exact three-term split of four values: hi / lo as packed fp16, the third terms (x 2^20) as four bf8 bytes.  The plain-subtraction form
 // of split_f16.h (split3_sub_pair), written out FOUR wide here: the two pairs' steps interleave, and issued pair after pair the staging
 // code of the GEMM, the partial convolution and the front kernel is scheduled differently (profiles/split_f16_refactor.md).
@@ -357,7 +360,8 @@ __device__ __forceinline__ void enh_split4_w(float4 v, float mul, uint2& w1, uin
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_f16s_mfma_kernel(const GemmArgs a) {
   constexpr int BM = 128, BN = 64, KC = 32, RB = 80, RT = 40;  // row bytes of the fp16 / bf8 planes
-  constexpr float WS = ENH_WS, WSI = 1.0f / ENH_WS;
+  fp16_ovfl_clamp();  // the A operand of Linear2 is a product of two hidden activations, bounded by nothing: saturate, never inf (split_f16.h)
+  const float WS = a.ws[0], WSI = a.ws[1];
   __shared__ __align__(16) unsigned char Ah[BM * RB], Al[BM * RB], At[BM * RT], B1[BN * RB], B2[BN * RB], B3[BN * RB], Bb[BN * RT];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, r = l & 31, h = l >> 5;
   const int ag = blockIdx.z;
@@ -607,7 +611,7 @@ struct EnhFrontArgs {
   const float* wsc;   // {scale of W1, 1 / it, scale of W2, 1 / it} (enh_wscale_kernel)
 };
 
-// Per-tensor power-of-two scales of the two Linear weight matrices for the f16 operand tables: ENH_WS = 2^12 for ordinary weights
+// Per-tensor power-of-two scales of the two Linear weight matrices for the f16 operand tables and gemm_f16s_mfma_kernel: ENH_WS = 2^12 for ordinary weights
 // (max |w| < 4: bit-identical to the static scale of round 3), smaller -- the largest power of two that keeps max |w| scale below 2^14 --
 // for larger ones: round 3 cast w * 4096 to fp16 unchecked, so a weight of magnitude >= 16 became inf in the table.
 // out = {s1, 1 / s1, s2, 1 / s2}; all-zero or non-finite maxima keep ENH_WS.  grid = 2 (one workgroup per tensor).

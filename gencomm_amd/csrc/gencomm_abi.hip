@@ -610,6 +610,29 @@ int gencomm_enhancer_fwd(const float* raw, const float* x, float* out, int n, in
     return fail(GC_ERR_WORKSPACE, "workspace too small (see gencomm_enhancer_workspace_bytes)");
   return enhancer_enqueue(p, raw, x, out, n, H, W, (char*)workspace, (hipStream_t)stream, modes_snapshot());
 }
+int gencomm_enhancer_workspace_layout(int n, int C, int H, int W, long long* byte_offsets) {
+  EnhancerPlan p;
+  if (const char* e = p.build(C)) return fail(GC_ERR_ARG, e);
+  GC_CHECK_ARG(n >= 1 && H >= 1 && W >= 1 && byte_offsets, "bad n/H/W or null pointer");
+  const EnhancerWs w = enhancer_ws(p, n, H, W);
+  const size_t off[8] = {w.Y, w.Z, w.Zc, w.Hd, w.G, w.O, w.colsum, w.gate};
+  for (int i = 0; i < 8; ++i) byte_offsets[i] = (long long)off[i];
+  return GC_OK;
+}
+int gencomm_enhancer_fwd_stages(const float* raw, const float* x, float* out, int n, int C, int H, int W,
+                                void* workspace, long long workspace_bytes, int first_stage, int last_stage, void* stream) {
+  EnhancerPlan p;
+  if (const char* e = p.build(C)) return fail(GC_ERR_ARG, e);
+  GC_CHECK_ARG(first_stage >= 1 && first_stage <= last_stage && last_stage <= 7, "stages are 1 .. 7, first <= last");
+  GC_CHECK_ARG(raw && workspace && (x || first_stage > 1) && (out || last_stage < 7), "null pointer");
+  GC_CHECK_ARG(n >= 1 && n <= 65535 && H >= 1 && W >= 1, "bad n/H/W");
+  if ((long long)enhancer_workspace_bytes(p, n, H, W) > workspace_bytes)
+    return fail(GC_ERR_WORKSPACE, "workspace too small (see gencomm_enhancer_workspace_bytes)");
+  const Modes m = modes_snapshot();
+  if (enh_range_cuts_fused_launch(enh_fuse_level(m, C), first_stage, last_stage))
+    return fail(GC_ERR_ARG, "the stage range cuts through a fused launch (K3-K4 under GENCOMM_MODE_ENH_FUSE 1, K3-K5 under 2)");
+  return enhancer_enqueue(p, raw, x, out, n, H, W, (char*)workspace, (hipStream_t)stream, m, first_stage, last_stage);
+}
 
 // ------------------------------------------------------------------------------------ message extractor
 int gencomm_msgext_num_params(int C) {

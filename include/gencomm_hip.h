@@ -284,6 +284,18 @@ long long gencomm_enhancer_workspace_bytes(int n, int C, int H, int W);
 /* out[n,C,H,W] = split_attn(block_1(x[n,C,H,W])) per agent (agents are independent). */
 int gencomm_enhancer_fwd(const float* raw, const float* x, float* out, int n, int C, int H, int W,
                          void* workspace, long long workspace_bytes, void* stream);
+/* Diagnostic entries for the kernel tests (additive to ABI v12).
+ * gencomm_enhancer_workspace_layout: byte offsets of the token-major intermediates inside the workspace, in the order
+ *   {Y = x + LN1(x) [n][HW][C], Z = LN2(Y), partial convolution applied in place [n][HW][C], Zc = Z[..., :C/4] before it [n][HW][C/4],
+ *    Hd = GELU(Linear1) [n][HW][4C], G = GELU(dw(x1)) x2 [n][HW][2C], O = Linear2 + Y [n][HW][C], colsum [n][C], gate [n][C]}.
+ *   O shares its storage with the front of Hd.
+ * gencomm_enhancer_fwd_stages: the launches of stages first_stage .. last_stage (inclusive) of gencomm_enhancer_fwd alone, on whatever
+ *   the workspace holds: 1 LayerNorms, 2 partial convolution, 3 Linear1 + GELU, 4 depthwise + gate, 5 Linear2 + residual + pool sums
+ *   (clears colsum first), 6 channel gate, 7 scale + transpose. x may be NULL when stage 1 is not run, out when stage 7 is not. A range
+ *   that cuts through a fused launch (3-4 under GENCOMM_MODE_ENH_FUSE 1, 3-5 under 2, both at C = 64 only) is GC_ERR_ARG. */
+int gencomm_enhancer_workspace_layout(int n, int C, int H, int W, long long* byte_offsets);
+int gencomm_enhancer_fwd_stages(const float* raw, const float* x, float* out, int n, int C, int H, int W,
+                                void* workspace, long long workspace_bytes, int first_stage, int last_stage, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * MessageExtractorv2 (opencood/models/gencomm_modules/message_extractor_v2.py:70-120): the producer
